@@ -18,9 +18,13 @@ and match counts; slamgpu_pack_frame_records_device) and RCCL-gathers them to ra
 collective's own stream, double-buffered so the gather of step k overlaps the compute of k+1
 (slam_framework_amd.dist.FrameGather). Weak scaling: F is fixed per rank.
 
-Prints ONE JSON line on rank 0 (driver contract), with `roofline` for the dominant kernel
-(HIP-event timed inside the timed region) and `cpu_baseline` (the oracle/ restatement on host
-cores, rank 0 only). Per-kernel breakdowns go to stderr.
+A plain run sets up, warms up, times `--steps` steps and prints ONE JSON line on rank 0 (driver
+contract): the headline `value` (stereo frames/s) and `ms_per_step`, the wall time of one timed
+step. `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs). `--full` adds everything else to the line: `roofline` for the dominant kernel
+(HIP-event timed inside the timed region), the per-kernel breakdown passes (also on stderr),
+`cpu_baseline` (the oracle/ restatement on host cores, rank 0 only) and the drop-in, optimizer and
+BoW legs.
 """
 from __future__ import annotations
 
@@ -231,12 +235,21 @@ def main():
     ap.add_argument("--no-alone", action="store_true",
                     help="skip the second breakdown pass (level 0's FAST after the pyramid): the "
                          "PMC passes use it so that every kernel's dispatches are the step's")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the per-kernel "
+                         "breakdown passes and rooflines, the CPU baseline, the drop-in, optimizer "
+                         "and BoW legs (each can be skipped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to "
+                         "DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"),
                     default=os.environ.get("SLAMGPU_BENCH_BACKEND", "nccl"),
                     help="process-group backend for N > 1: nccl (RCCL, one GPU per rank; the "
                          "driver's runs) or gloo (the gather staged through host memory; ranks "
                          "may share a GPU -- exercises the N-rank path on a one-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -300,37 +313,40 @@ def main():
     print(f"[rank {rank}] keypoints/image {nk.tolist()} queries/frame {nq[1:5].tolist()} "
           f"matches/frame {nm[1:5].tolist()}", file=sys.stderr)
 
-    # ---- per-kernel breakdown pass (untimed) to pick the dominant kernel
-    names = ["pyr_down", "fast_cells", "octree", "octree_global", "orient_desc", "stereo_rows",
-             "stereo_match", "stereo_median", "grid_build", "vo_queries", "search_cand",
-             "search_resolve"]
-    torch.cuda.synchronize()
-    ctx.timing_start("*", 4096)
-    step(group=0)
-    ctx.timing_stop()
-    brk = {n: ctx.timing_read(n) for n in names}
-    tot = sum(v[0] for v in brk.values())
-    print("[rank %d] kernel ms/step: " % rank + ", ".join(
-        f"{n} {brk[n][0]:.3f} ({100 * brk[n][0] / tot:.0f}%)" for n in names), file=sys.stderr)
-    dominant = max(names, key=lambda n: brk[n][0])
-    # the same pass with level 0's FAST after the pyramid instead of beside it (a side stream in
-    # the step): every kernel alone, the basis of the per-kernel pipe fractions (the PMC pass
-    # serialises dispatches too); the step itself keeps the fork
-    alone = brk
-    if not args.no_alone:
-        for c in ctxs:
-            c.set_extract_fork(False)
+    brk = alone = dominant = None
+    if args.full:
+        # ---- per-kernel breakdown pass (untimed) to pick the dominant kernel
+        names = ["pyr_down", "fast_cells", "octree", "octree_global", "orient_desc", "stereo_rows",
+                 "stereo_match", "stereo_median", "grid_build", "vo_queries", "search_cand",
+                 "search_resolve"]
         torch.cuda.synchronize()
         ctx.timing_start("*", 4096)
         step(group=0)
         ctx.timing_stop()
-        alone = {n: ctx.timing_read(n) for n in names}
-        for c in ctxs:
-            c.set_extract_fork(True)
+        brk = {n: ctx.timing_read(n) for n in names}
+        tot = sum(v[0] for v in brk.values())
+        print("[rank %d] kernel ms/step: " % rank + ", ".join(
+            f"{n} {brk[n][0]:.3f} ({100 * brk[n][0] / tot:.0f}%)" for n in names), file=sys.stderr)
+        dominant = max(names, key=lambda n: brk[n][0])
+        # the same pass with level 0's FAST after the pyramid instead of beside it (a side stream
+        # in the step): every kernel alone, the basis of the per-kernel pipe fractions (the PMC
+        # pass serialises dispatches too); the step itself keeps the fork
+        alone = brk
+        if not args.no_alone:
+            for c in ctxs:
+                c.set_extract_fork(False)
+            torch.cuda.synchronize()
+            ctx.timing_start("*", 4096)
+            step(group=0)
+            ctx.timing_stop()
+            alone = {n: ctx.timing_read(n) for n in names}
+            for c in ctxs:
+                c.set_extract_fork(True)
 
-    # ---- timed region
-    launches_per_step = max(1, brk[dominant][1])
-    ctx.timing_start(dominant, launches_per_step * args.steps + 16)
+    # ---- timed region (--full: the dominant kernel's launches HIP-event timed inside it)
+    if args.full:
+        launches_per_step = max(1, brk[dominant][1])
+        ctx.timing_start(dominant, launches_per_step * args.steps + 16)
     bench_stream = torch.cuda.current_stream(dev).cuda_stream
     if world > 1:
         dist.barrier()
@@ -339,7 +355,7 @@ def main():
     torch.cuda.synchronize()        # (tools/stats_timed.py); outside the timed interval
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last_group = step()
     if gat is not None:
         gat.wait_all()
     torch.cuda.synchronize()
@@ -347,10 +363,14 @@ def main():
         dist.barrier()
     t1 = time.perf_counter()
     G.trace_marker(2, bench_stream)
-    ctx.timing_stop()
+    if args.full:
+        ctx.timing_stop()
     job.sync()
     elapsed = SD.max_over_ranks(t1 - t0, dev)
-    dom_ms, dom_n = ctx.timing_read(dominant)
+    if args.full:
+        dom_ms, dom_n = ctx.timing_read(dominant)
+    if args.dump_outputs and rank == 0:  # before any later leg reuses the contexts
+        dump_outputs(args.dump_outputs, job, last_group)
     # per-rank result summary gathered to every rank (validation, outside the timed region)
     summ = SD.gather_summary([int(nk.sum()), int(nm.sum()), int(nq.sum())], dev)
 
@@ -360,6 +380,31 @@ def main():
 
     gather_info = job.check_gather() if gat is not None else None
     if rank == 0:
+        line = {
+            "metric": "stereo frames/sec ORB extract+match @1241x376, 2000 kp/frame",
+            "value": round(value, 2), "unit": "stereo frames/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic (seeded layered-surfaces scene: ~50% of keypoints with stereo "
+                    "depth, ~1000 frame-to-frame queries/frame; camera turning + 0.3 m/frame "
+                    "forward; one sequence of 16 renders played back and forth, sharded over the "
+                    "ranks)",
+            "config": {"workload": "configs[1]: synthetic 1241x376 stereo stream, 2000 kp/frame, "
+                                   "extract L+R + stereo match + frame-to-frame match",
+                       "frames_per_gpu_per_step": NS * (Bs - 1), "batch": B, "streams": NS,
+                       "batches_in_flight": INF,
+                       "nfeatures": 2000,
+                       "nlevels": 8, "scale_factor": 1.2, "fast_th": [20, 7],
+                       "parallelism": f"frame-sharded x{world}" + (
+                           ", contiguous shards + 1 halo frame, " + (
+                               "gloo gather through host memory to rank 0" if gloo else
+                               "RCCL gather to rank 0") if world > 1 else ""),
+                       "dist_backend": (args.dist_backend if world > 1 else None)},
+            "gather": gather_info,
+            "per_rank_matches_per_step": summ[:, 1].tolist(),
+            "full": args.full,
+        }
+    if rank == 0 and args.full:
         level_px = [ctx.pyramid_level(0, l).size for l in range(8)]
         kp_img = float(nk.mean())
         nqueries = int(nq.sum())
@@ -506,27 +551,7 @@ def main():
                 "over the kernel's alone time per step, LDS / MFMA busy of the PMC pass's "
                 "serialised dispatch, profiles/pipes.json); the timed-region figures are in hbm / "
                 "valu_mix")
-        line = {
-            "metric": "stereo frames/sec ORB extract+match @1241x376, 2000 kp/frame",
-            "value": round(value, 2), "unit": "stereo frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic (seeded layered-surfaces scene: ~50% of keypoints with stereo "
-                    "depth, ~1000 frame-to-frame queries/frame; camera turning + 0.3 m/frame "
-                    "forward; one sequence of 16 renders played back and forth, sharded over the "
-                    "ranks)",
-            "config": {"workload": "configs[1]: synthetic 1241x376 stereo stream, 2000 kp/frame, "
-                                   "extract L+R + stereo match + frame-to-frame match",
-                       "frames_per_gpu_per_step": NS * (Bs - 1), "batch": B, "streams": NS,
-                       "batches_in_flight": INF,
-                       "nfeatures": 2000,
-                       "nlevels": 8, "scale_factor": 1.2, "fast_th": [20, 7],
-                       "parallelism": f"frame-sharded x{world}" + (
-                           ", contiguous shards + 1 halo frame, " + (
-                               "gloo gather through host memory to rank 0" if gloo else
-                               "RCCL gather to rank 0") if world > 1 else ""),
-                       "dist_backend": (args.dist_backend if world > 1 else None)},
-            "gather": gather_info,
+        line.update({
             "roofline": roofline,
             "path_roofline": path_roof,
             "cpu_baseline": cpu,
@@ -535,12 +560,73 @@ def main():
             "optimizer": opt,
             "bow": bow_leg,
             "drop_in": drop_in,
-            "per_rank_matches_per_step": summ[:, 1].tolist(),
-        }
+        })
+    if rank == 0:
         print(json.dumps(line))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+KP_FIELDS = ("x", "y", "size", "angle", "response", "octave", "class_id")  # slamgpu.KP_DTYPE
+DUMP_FRAMES = 48  # batch slots whose full per-keypoint results --dump-outputs writes (~0.7 MB each)
+
+
+def dump_outputs(out_dir, job, group):
+    """--dump-outputs: what the step that ran on in-flight group `group` left for its caller,
+    downloaded through the Context's own accessors after job.sync() and written as
+    DIR/<name>.npy. The inputs are the seeded synthetic sequence, so two builds run with the same
+    arguments can be compared array for array. Slot s of the batch is global frame job.gframe[s];
+    slot 0 of each context is the halo frame, whose frame-to-frame search is not part of the
+    result (written as no match).
+      n_keypoints [B, 2], n_matches [B]              every slot (float64)
+      frames [S]                                     the slots below: DUMP_FRAMES spread evenly
+      keypoints [S, 2, kp_cap, 7]                    left / right view; x, y, size, angle,
+                                                     response, octave, class_id (float32)
+      descriptors [S, 2, kp_cap, 32]                 one value per byte (float32)
+      u_right, depth [S, kp_cap]                     stereo coordinates (float32)
+      map_point [S, kp_cap]                          frame-to-frame match ids, -1 = none (float64)
+    Rows past a view's keypoint count are 0 (map_point: -1)."""
+    ctxs, _, parts = job.groups[group]
+    Bs, kc, B = job.Bs, job.kc, job.B
+    per_slot = kc * (2 * 4 * (len(KP_FIELDS) + 32) + 2 * 4 + 8)  # bytes of one slot's rows below
+    n_pick = max(1, min(B, DUMP_FRAMES, (48 << 20) // per_slot))  # well under 64 MB in all
+    pick = np.unique(np.linspace(0, B - 1, n_pick).round().astype(np.int64))
+    row = {int(s): j for j, s in enumerate(pick)}
+    S_ = len(pick)
+    n_kp = np.zeros((B, 2), np.float64)
+    n_m = np.zeros(B, np.float64)
+    kps = np.zeros((S_, 2, kc, len(KP_FIELDS)), np.float32)
+    desc = np.zeros((S_, 2, kc, 32), np.float32)
+    ur = np.zeros((S_, kc), np.float32)
+    depth = np.zeros((S_, kc), np.float32)
+    mp = np.full((S_, kc), -1.0, np.float64)
+    for si, c in enumerate(ctxs):
+        d_mp = parts[si]["mp"].cpu().numpy().reshape(Bs, kc)
+        d_nm = parts[si]["nm"].cpu().numpy()
+        for i in range(Bs):
+            s = si * Bs + i
+            views = [c.keypoints(2 * i + v) for v in range(2)]
+            n_kp[s] = [len(k) for k, _ in views]
+            if i:
+                n_m[s] = d_nm[i]
+            j = row.get(s)
+            if j is None:
+                continue
+            for v, (k, d) in enumerate(views):
+                for fi, name in enumerate(KP_FIELDS):
+                    kps[j, v, :len(k), fi] = k[name]
+                desc[j, v, :len(d)] = d
+            u, z = c.stereo(i)
+            ur[j, :len(u)], depth[j, :len(z)] = u, z
+            if i:
+                nl = len(views[0][0])
+                mp[j, :nl] = d_mp[i, :nl]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("frames", pick.astype(np.float64)), ("n_keypoints", n_kp),
+                    ("n_matches", n_m), ("keypoints", kps), ("descriptors", desc),
+                    ("u_right", ur), ("depth", depth), ("map_point", mp)):
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def spawn_ranks(n):

@@ -220,7 +220,7 @@ def test_bench_two_ranks_gloo():
     the driver's multi-GPU runs."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--steps", "2", "--warmup", "1", "--batch", "32", "--no-cpu-baseline",
+           "--steps", "2", "--warmup", "1", "--batch", "32", "--full", "--no-cpu-baseline",
            "--no-optimizer", "--no-bow", "--no-latency"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=150,
                        env=dict(os.environ, PYTHONUNBUFFERED="1"))
@@ -235,3 +235,65 @@ def test_bench_two_ranks_gloo():
     assert g["identical"] is True and g["frames_checked_vs_rank0"] > 0, g
     assert len(d["per_rank_matches_per_step"]) == 2 and min(d["per_rank_matches_per_step"]) > 0
     assert d["value"] > 0 and d["roofline"]["avg_launch_us"] > 0
+
+
+def test_bench_plain_run_dumps_last_step(gpu_lib, tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full): ONE JSON line with the headline figure and
+    ms_per_step for the --steps it was given and none of the --full legs, and --dump-outputs
+    writes the last timed step's results -- float32 / float64 .npy files that equal, value for
+    value, what the same ShardedFrontend job computes in this process (two contexts of 3 slots,
+    slot 0 of each the halo frame: no search result)."""
+    import json
+    import torch
+    from slam_framework_amd.sharded import ShardedFrontend
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3",
+           "--warmup", "1", "--batch", "6", "--streams", "2", "--distinct", "4",
+           "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=150,
+                       env=dict(os.environ, PYTHONUNBUFFERED="1"))
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["n_gpus"] == 1 and d["full"] is False
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "stereo frames/s" and d["dtype"] == "u8"
+    assert abs(d["value"] - 4 * 1000.0 / d["ms_per_step"]) <= 0.01 * d["value"]
+    for k in ("roofline", "cpu_baseline", "kernels_standalone", "optimizer", "bow", "drop_in"):
+        assert k not in d
+    out = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in sorted(os.listdir(tmp_path))}
+    assert sorted(out) == ["depth", "descriptors", "frames", "keypoints", "map_point",
+                           "n_keypoints", "n_matches", "u_right"]
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert out["frames"].tolist() == [0, 1, 2, 3, 4, 5]
+
+    dev = torch.device("cuda", 0)
+    Ls, Rs = S.layered_sequence(1000, 4)
+    with torch.cuda.stream(torch.cuda.Stream(device=dev)):
+        job = ShardedFrontend(Ls, Rs, CAM, 6, dev, streams=2, inflight=1)
+        job.step()
+        job.sync()
+    own = job.own_results(0)
+    assert sorted(own) == [1, 2, 3, 4]
+    fields = ("x", "y", "size", "angle", "response", "octave", "class_id")
+    for slot in range(6):
+        halo = slot % 3 == 0
+        if halo:
+            assert out["n_matches"][slot] == 0 and (out["map_point"][slot] == -1).all()
+            continue
+        r = own[int(job.gframe[slot])]
+        nl, nr = len(r["kps_left"]), len(r["kps_right"])
+        assert out["n_keypoints"][slot].tolist() == [nl, nr] and nl > 1000
+        for v, (k, de) in enumerate(((r["kps_left"], r["desc_left"]),
+                                     (r["kps_right"], r["desc_right"]))):
+            got = out["keypoints"][slot, v]
+            want = np.stack([k[f].astype(np.float32) for f in fields], 1)
+            assert np.array_equal(got[:len(k)], want) and not got[len(k):].any()
+            assert np.array_equal(out["descriptors"][slot, v, :len(k)], de.astype(np.float32))
+        assert np.array_equal(out["u_right"][slot, :nl], r["u_right"])
+        assert np.array_equal(out["depth"][slot, :nl], r["depth"])
+        assert np.array_equal(out["map_point"][slot, :nl], r["map_point"].astype(np.float64))
+        assert (out["map_point"][slot, nl:] == -1).all()
+        assert out["n_matches"][slot] == r["nmatches"] > 0

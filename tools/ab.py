@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 argv = sys.argv[1:]
-extra = ["--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-optimizer"]
+extra = ["--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-optimizer"]
 if "--" in argv:
     i = argv.index("--")
     argv, extra = argv[:i], argv[i + 1:]

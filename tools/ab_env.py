@@ -10,7 +10,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 argv = sys.argv[1:]
-extra = ["--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-optimizer", "--no-bow"]
+extra = ["--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-optimizer", "--no-bow"]
 if "--" in argv:
     i = argv.index("--")
     argv, extra = argv[:i], argv[i + 1:]

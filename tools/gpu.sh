@@ -4,8 +4,8 @@
 # Steps (each under its own time limit; the first failing step ends the call):
 #   tests[=PATHS]   pytest -m gpu (default: the whole suite)
 #   smoke           __graft_entry__.smoke()
-#   bench           python3 bench.py (default line) -> bench.json
-#   quick           python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-optimizer
+#   bench           python3 bench.py --full (every leg) -> bench.json
+#   quick           python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-optimizer
 #   stats           rocprofv3 --kernel-trace --stats of the default bench + the timed-region split
 #   traffic         FETCH_SIZE / WRITE_SIZE passes (tools/pmc_traffic.sh)
 #   pipes           two --pmc passes of pipe counters (tools/pmc_pipes.sh -> tools/pipes.py)
@@ -19,7 +19,7 @@ export TMPDIR=/tmp
 TAG=$1; shift
 O=gpurun_out/$TAG
 mkdir -p $O
-QUICK="--steps 10 --warmup 2 --no-cpu-baseline --no-optimizer"
+QUICK="--full --steps 10 --warmup 2 --no-cpu-baseline --no-optimizer"
 for s in "$@"; do
   case $s in
     tests|tests=*)
@@ -34,7 +34,7 @@ for s in "$@"; do
         || { echo "smoke rc=$?"; tail -5 $O/smoke.log; exit 1; }
       tail -1 $O/smoke.log ;;
     bench)
-      timeout -k 10 300 python3 bench.py > $O/bench.json 2> $O/bench.err \
+      timeout -k 10 300 python3 bench.py --full > $O/bench.json 2> $O/bench.err \
         || { echo "bench rc=$?"; tail -5 $O/bench.err; exit 1; }
       tail -c 300 $O/bench.json ;;
     quick)
@@ -43,7 +43,7 @@ for s in "$@"; do
       python3 -c "import json,sys; d=json.loads(open('$O/quick.json').read().strip().splitlines()[-1]); print(d['ms_per_step'], d['value'], d.get('kernel_ms_per_step'))" ;;
     stats)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- \
-        python3 bench.py > $O/stats_bench.json 2> $O/stats.log || { echo "rocprof rc=$?"; exit 1; }
+        python3 bench.py --full > $O/stats_bench.json 2> $O/stats.log || { echo "rocprof rc=$?"; exit 1; }
       f=$(ls $O/stats/*/run_kernel_trace.csv $O/stats/run_kernel_trace.csv 2>/dev/null | head -1)
       [ -n "$f" ] && python3 tools/stats_timed.py $f > $O/timed_kernel_stats.csv
       echo "stats ok" ;;
@@ -56,7 +56,7 @@ for s in "$@"; do
     pmc=*)
       grp=${s#pmc=}; name=$(basename $grp .txt)
       timeout -s KILL 200 rocprofv3 --pmc $(cat $grp) --kernel-trace --output-format csv \
-        -d $O/pmc_$name -o run -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline \
+        -d $O/pmc_$name -o run -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline \
         --no-optimizer > $O/pmc_$name.log 2>&1 || { echo "pmc $name rc=$?"; exit 1; }
       echo "pmc $name ok" ;;
     ab=*)

@@ -7,7 +7,7 @@ set -e
 export TMPDIR=/tmp
 K=${KERNEL:-fast_cells}
 OUT=${OUT:-gpurun_out/pmck/$K}
-ARGS=${ARGS:-"--steps 2 --warmup 1 --no-cpu-baseline"}
+ARGS=${ARGS:-"--full --steps 2 --warmup 1 --no-cpu-baseline"}
 CMD=${CMD:-"python3 bench.py $ARGS"}
 mkdir -p $OUT
 i=0

@@ -4,7 +4,7 @@
 set -e
 export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/pmc}
-ARGS=${ARGS:-"--steps 2 --warmup 1 --no-cpu-baseline"}
+ARGS=${ARGS:-"--full --steps 2 --warmup 1 --no-cpu-baseline"}
 mkdir -p $OUT
 i=0
 for grp in \

@@ -2,13 +2,13 @@
 in-step kernel split): python3 tools/sweep.py --inflight,2 --inflight,3,--streams,2 ...
 (commas separate the arguments of one set: tools/gpu.sh py=tools/sweep.py:SET:SET ...;
 KEY=VALUE tokens go to the environment, LIB=path picks a library build)
-Every run adds the quick flags (--steps 10 --warmup 2 --no-cpu-baseline --no-optimizer)."""
+Every run adds the quick flags (--full --steps 10 --warmup 2 --no-cpu-baseline --no-optimizer)."""
 import json
 import os
 import subprocess
 import sys
 
-QUICK = ["--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-optimizer"]
+QUICK = ["--full", "--steps", "10", "--warmup", "2", "--no-cpu-baseline", "--no-optimizer"]
 
 
 def main(argsets):
