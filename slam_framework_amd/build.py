@@ -38,6 +38,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not _stale():
         build_capi_check()
         build_adapter_check()
+        build_geometry_check()
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -64,6 +65,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.replace(tmp, LIB)
     build_capi_check()
     build_adapter_check()
+    build_geometry_check()
     return LIB
 
 
@@ -104,6 +106,27 @@ def build_adapter_check() -> str:
                     os.path.join(ROOT, "include"), ADAPTER_SRC, "-L", PKG, "-lslamgpu",
                     "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", ADAPTER_BIN], check=True)
     return ADAPTER_BIN
+
+
+GEOMETRY_SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")
+GEOMETRY_BIN = os.path.join(ROOT, "tests", "geometry_check")
+
+
+def build_geometry_check() -> str:
+    """Host-only hipcc build (orb_geometry.h includes hip_runtime.h) of tests/geometry_check.cpp +
+    csrc/orb_geometry.cpp: compute_geometry / build_cells printed as JSON, no device code and no
+    libslamgpu.so. Same -ffp-contract=off as the library."""
+    geo = os.path.join(CSRC, "orb_geometry.cpp")
+    deps = [GEOMETRY_SRC, geo] + glob.glob(os.path.join(CSRC, "orb_*.h"))
+    if os.path.exists(GEOMETRY_BIN) and os.path.getmtime(GEOMETRY_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return GEOMETRY_BIN
+    tmp = GEOMETRY_BIN + ".tmp"
+    subprocess.run([HIPCC, "-x", "hip", "--offload-host-only", "-O2", "-std=c++17",
+                    "-ffp-contract=off", "-Wall", "-I", CSRC, GEOMETRY_SRC, geo, "-o", tmp],
+                   check=True)
+    os.replace(tmp, GEOMETRY_BIN)
+    return GEOMETRY_BIN
 
 
 if __name__ == "__main__":

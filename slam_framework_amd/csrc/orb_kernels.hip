@@ -1654,13 +1654,22 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
   // registers. Otherwise two sweeps over global memory (count, then place).
   const float hX = L.hx;
   constexpr int kGatherChunks = 8, kGatherRegs = 48;
+  // key groups of the fast path's <= 64 * kGatherChunks cells (64 with the default kCellGroup 8,
+  // 128 with -DFAST_CELLS_PER_WAVE=4): the search below starts at kMaxGroups / 2, so it reaches
+  // every group index < kMaxGroups. gp[] borrows the level's sort scratch (NC >= ncell + 1 u32,
+  // checked at run time; ng <= ncell), which the static bound below keeps a group table inside.
+  constexpr int kMaxGroups = 64 * kGatherChunks / kCellGroup;
+  static_assert(kMaxGroups >= 2 && (kMaxGroups & (kMaxGroups - 1)) == 0,
+                "the gather's binary search halves its step from kMaxGroups / 2 down to 1");
+  static_assert(kMaxGroups <= 64 * kGatherChunks,
+                "gp[] (one int per key group) must fit the ncell + 1 <= NC sort keys it borrows");
   int bcnt = 0;  // lane b < nIni: keys in bucket b
   if (ncell <= 64 * kGatherChunks && K <= 64 * kGatherRegs && ncell + 1 <= NC) {
     // key-group prefixes in LDS (the level's sort scratch, free until the passes): a group's
     // keys are contiguous from its first slot, so a key slot needs only its group -- the
     // largest g with gp[g] <= s (empty groups repeat the next prefix and are skipped) -- found by
-    // a branch-free binary search over the <= 64 groups whose probes for all the wave's slots
-    // are issued together, step by step, then every key load at once
+    // a branch-free binary search over the <= kMaxGroups groups whose probes for all the wave's
+    // slots are issued together, step by step, then every key load at once
     int* const gp = reinterpret_cast<int*>(sortk);
     int ccnt[kGatherChunks];
 #pragma unroll
@@ -1682,13 +1691,13 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
     const int R = (K + 63) >> 6;
-    const int ng = (ncell + kCellGroup - 1) / kCellGroup;  // <= 64
+    const int ng = (ncell + kCellGroup - 1) / kCellGroup;  // <= kMaxGroups
     uint32_t kr[kGatherRegs];
     int br[kGatherRegs];  // the slot's group during the search, its bucket after
 #pragma unroll
     for (int r = 0; r < kGatherRegs; r++) br[r] = 0;
 #pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) {
+    for (int step = kMaxGroups / 2; step >= 1; step >>= 1) {
 #pragma unroll
       for (int r = 0; r < kGatherRegs; r++) {
         if (r < R) {
@@ -2880,16 +2889,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void o
   };
   // The window of a keypoint into the wave's staging area: slot 64 i + lane (16 bytes) holds row
   // 16 i + (lane >> 2) (rows past 42 repeat row 42), chunk (lane & 3) ^ swz(row). Fast path: three
-  // buffer-to-LDS loads off the (wave-uniform) window origin, bounded by the window's 43 rows
-  // (pitch >= 64: every load is inside them; bytes past x + 24 only feed output columns past the
-  // table's 40). Border windows (reflect-101 rows and columns) gather bytes into the same slots.
+  // buffer-to-LDS loads off the (wave-uniform) window origin xa = (x - 21) & ~3. The table's 40
+  // columns are the row sums of window bytes 0 .. 45 (columns x - 21 .. x + 24 at most), so chunk 3
+  // (bytes 48 .. 63, up to column x + 42 <= w + 11) only feeds output columns 42 and up, which
+  // nothing reads. In rows 0 .. 41 that over-read ends inside the level's next row (w >= 46 > 11,
+  // and row 42 <= h - 1 exists); on row 42, which fastp lets be the level's last row, it would
+  // leave the image -- past the caller's buffer with pitch == cols -- so row 42's chunk-3 slots load
+  // chunk 2 again. Every fast-path load then lies inside [org, level + (h - 1) * pitch + w):
+  // row 42 ends at column xa + 47 <= x + 26 <= w - 5. Border windows (reflect-101 rows and
+  // columns) gather bytes into the same slots.
   uint8_t* win = &s_win[wid][0];
   uint32_t dma_row[3], dma_off[3], a_lds[3];
 #pragma unroll
   for (int i = 0; i < 3; i++) {
     const int r = 16 * i + (lane >> 2);
     dma_row[i] = (uint32_t)min(r, 42);
-    dma_off[i] = 16u * (uint32_t)((lane & 3) ^ win_swz(r));
+    const uint32_t chunk = (uint32_t)((lane & 3) ^ win_swz(r));
+    dma_off[i] = 16u * (r >= 42 && chunk == 3u ? 2u : chunk);
     // the A read of tile row i: row arow[i], chunk g
     a_lds[i] = 16u * (4u * arow[i] + (uint32_t)(mf_g ^ win_swz((int)arow[i])));
   }
