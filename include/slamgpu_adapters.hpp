@@ -23,6 +23,7 @@
 #include "slamgpu.h"
 #include "slamgpu_bow.h"
 #include "slamgpu_kfmatch.h"
+#include "slamgpu_loopmatch.h"
 #include "slamgpu_optimizer.h"
 
 namespace slamgpu_adapter {
@@ -978,6 +979,200 @@ inline int global_bundle_adjustment(LocalBaGraph& g, const slamgpu_camera& cam,
                                             robust ? 1 : 0, stop_flag, &its),
            slamgpu_optimizer_last_error);
   return its;
+}
+
+// ---- the LoopCloser's three Sim3 matchers (slamgpu_loopmatch.h) ----------------------------------
+// The decomposed transforms stay with the caller's OpenCV arithmetic: Scw as the reference splits
+// it at orb_matcher.cpp:393-397 / :965-969, S12 as :1103-1105 makes sR12, sR21 and t21.
+struct ScwBlocks {
+  float Rcw[9], tcw[3], Ow[3];
+};
+struct Sim3Blocks {
+  float sR12[9], t12[3], sR21[9], t21[3];
+};
+
+inline slamgpu_kf loop_kf(const KeyFrameView& v, const KeyFrameFeatures& f, const float* Rcw,
+                          const float* tcw, const float* Ow) {
+  slamgpu_kf k;
+  std::memset(&k, 0, sizeof(k));
+  k.kps = v.undist_kps;
+  k.desc = f.desc;
+  k.n = v.n_kps;
+  for (int i = 0; i < 9; ++i) k.Rcw[i] = Rcw[i];
+  for (int i = 0; i < 3; ++i) {
+    k.tcw[i] = tcw[i];
+    k.Ow[i] = Ow ? Ow[i] : 0.0f;
+  }
+  return k;
+}
+// The keyframe at its own pose (SearchBySim3 reads GetRotation() / GetTranslation()).
+inline slamgpu_kf loop_kf(const KeyFrameView& v, const KeyFrameFeatures& f) {
+  float R[9], t[3];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R[3 * r + c] = v.Tcw[4 * r + c];
+    t[r] = v.Tcw[4 * r + 3];
+  }
+  return loop_kf(v, f, R, t, f.Ow);
+}
+
+// Map point m as the matchers read it (m < 0: an empty record with skip set).
+inline slamgpu_fuse_point loop_point(const MapPointView* mps, const MapPointGeometry* geom, int m,
+                                     bool skip) {
+  slamgpu_fuse_point q;
+  std::memset(&q, 0, sizeof(q));
+  q.skip = m < 0 || skip;
+  if (m < 0) return q;
+  std::memcpy(q.xyz, mps[m].xyz, sizeof(q.xyz));
+  std::memcpy(q.normal, geom[m].normal, sizeof(q.normal));
+  q.min_dist = geom[m].min_dist;
+  q.max_dist = geom[m].max_dist;
+  std::memcpy(q.desc, mps[m].desc, 32);
+  return q;
+}
+
+// ---- OrbMatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (orb_matcher.cpp:956-1079),
+// LoopCloser::SearchAndFuse (loop_closer.cpp:484, th = 4). replace[i] = the map point the caller
+// writes into vpReplacePoint[i] (-1: leave it); added = the (point, keypoint) pairs of
+// pMP->AddObservation(pKF, idx); pKF->AddMapPoint(pMP, idx), in order.
+struct FuseSim3Result {
+  int nfused = 0;
+  std::vector<int32_t> replace;
+  std::vector<std::pair<int32_t, int32_t>> added;
+};
+// The tail :1061-1075 over the candidate search's result. `slot` is the keyframe's map point per
+// keypoint (updated by the AddMapPoint calls). A point that is bad or sits in a slot by now is
+// passed over: inside one call that restates spAlreadyFound (nothing in the loop makes a point
+// bad), across a SearchAndFuse batch it is the re-check the earlier keyframes' Replace calls need.
+inline FuseSim3Result fuse_sim3_apply(const int32_t* best_idx, const int32_t* points,
+                                      int n_points, const uint8_t* bad,
+                                      std::vector<int32_t>& slot,
+                                      const std::vector<uint8_t>& in_kf_at_entry) {
+  FuseSim3Result res;
+  res.replace.assign(n_points > 0 ? n_points : 0, -1);
+  for (int i = 0; i < n_points; ++i) {
+    const int m = points[i];
+    if (m < 0 || bad[m] || in_kf_at_entry[i] || best_idx[i] < 0) continue;
+    const int j = best_idx[i], cur = slot[j];
+    if (cur >= 0) {
+      if (!bad[cur]) res.replace[i] = cur;
+    } else {
+      slot[j] = m;
+      res.added.emplace_back(m, j);
+    }
+    res.nfused++;
+  }
+  return res;
+}
+inline FuseSim3Result fuse_sim3(const KeyFrameView& kf, const KeyFrameFeatures& kff,
+                                const ScwBlocks& scw, const MapPointView* mps,
+                                const MapPointGeometry* geom, const int32_t* points, int n_points,
+                                float th, const slamgpu_camera& cam, const slamgpu_levels& lv,
+                                const slamgpu_kf_grid& grid) {
+  // spAlreadyFound = pKF->GetMapPoints() (:972)
+  auto in_kf = [&](int m) {
+    for (int i = 0; i < kf.n_kps; ++i)
+      if (kf.map_points[i] == m) return true;
+    return false;
+  };
+  std::vector<slamgpu_fuse_point> pts(n_points > 0 ? n_points : 1);
+  std::vector<uint8_t> found(n_points > 0 ? n_points : 1), bad(1);
+  int max_m = -1;
+  for (int i = 0; i < n_points; ++i) max_m = points[i] > max_m ? points[i] : max_m;
+  for (int i = 0; i < kf.n_kps; ++i) max_m = kf.map_points[i] > max_m ? kf.map_points[i] : max_m;
+  bad.assign(max_m + 2, 0);
+  for (int m = 0; m <= max_m; ++m) bad[m] = mps[m].bad;
+  for (int i = 0; i < n_points; ++i) {
+    const int m = points[i];
+    found[i] = m >= 0 && in_kf(m);
+    pts[i] = loop_point(mps, geom, m, m >= 0 && (mps[m].bad || found[i]));
+  }
+  const slamgpu_kf k = loop_kf(kf, kff, scw.Rcw, scw.tcw, scw.Ow);
+  std::vector<int32_t> best(n_points > 0 ? n_points : 1), dist(n_points > 0 ? n_points : 1);
+  int nf = 0;
+  throw_if(slamgpu_fuse_sim3(&k, pts.data(), n_points, th, &cam, &lv, &grid, best.data(),
+                             dist.data(), &nf),
+           slamgpu_loopmatch_last_error);
+  std::vector<int32_t> slot(kf.map_points, kf.map_points + kf.n_kps);
+  return fuse_sim3_apply(best.data(), points, n_points, bad.data(), slot, found);
+}
+
+// ---- OrbMatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (orb_matcher.cpp:384-497),
+// LoopCloser::ComputeSim3 (loop_closer.cpp:441, th = 10). vpMatched: map point index per
+// keypoint (-1 = none), updated in place as :490 does. Returns nmatches.
+inline int search_by_projection_sim3(const KeyFrameView& kf, const KeyFrameFeatures& kff,
+                                     const ScwBlocks& scw, const MapPointView* mps,
+                                     const MapPointGeometry* geom, const int32_t* points,
+                                     int n_points, int32_t* vpMatched, float th,
+                                     const slamgpu_camera& cam, const slamgpu_levels& lv,
+                                     const slamgpu_kf_grid& grid) {
+  const int n = kf.n_kps;
+  std::vector<uint8_t> matched_in(n > 0 ? n : 1);
+  for (int j = 0; j < n; ++j) matched_in[j] = vpMatched[j] >= 0;
+  auto already_found = [&](int m) {  // spAlreadyFound (:400-401)
+    for (int j = 0; j < n; ++j)
+      if (vpMatched[j] == m) return true;
+    return false;
+  };
+  std::vector<slamgpu_fuse_point> pts(n_points > 0 ? n_points : 1);
+  for (int i = 0; i < n_points; ++i) {
+    const int m = points[i];
+    pts[i] = loop_point(mps, geom, m, m >= 0 && (mps[m].bad || already_found(m)));
+  }
+  const slamgpu_kf k = loop_kf(kf, kff, scw.Rcw, scw.tcw, scw.Ow);
+  std::vector<int32_t> kp_point(n > 0 ? n : 1), point_kp(n_points > 0 ? n_points : 1);
+  int nm = 0;
+  throw_if(slamgpu_search_by_projection_sim3(&k, pts.data(), n_points, matched_in.data(), th,
+                                             &cam, &lv, &grid, kp_point.data(), point_kp.data(),
+                                             &nm),
+           slamgpu_loopmatch_last_error);
+  for (int j = 0; j < n; ++j)
+    if (kp_point[j] >= 0) vpMatched[j] = points[kp_point[j]];
+  return nm;
+}
+
+// ---- OrbMatcher::SearchBySim3 (orb_matcher.cpp:1081-1310), LoopCloser::ComputeSim3
+// (loop_closer.cpp:382, th = 7.5). vpMatches12: pKF2's map point index per pKF1 feature (-1 =
+// none), updated in place where both directions agree (:1291-1307). Returns nFound.
+inline int search_by_sim3(int kf1_index, int kf2_index, const KeyFrameView* kfs,
+                          const KeyFrameFeatures& f1, const KeyFrameFeatures& f2,
+                          const MapPointView* mps, const MapPointGeometry* geom,
+                          int32_t* vpMatches12, const Sim3Blocks& s, float th,
+                          const slamgpu_camera& cam, const slamgpu_levels& lv,
+                          const slamgpu_kf_grid& grid) {
+  const KeyFrameView& kf1 = kfs[kf1_index];
+  const KeyFrameView& kf2 = kfs[kf2_index];
+  const int n1 = kf1.n_kps, n2 = kf2.n_kps;
+  std::vector<slamgpu_fuse_point> mp1(n1 > 0 ? n1 : 1), mp2(n2 > 0 ? n2 : 1);
+  std::vector<uint8_t> already1(n1 > 0 ? n1 : 1, 0), already2(n2 > 0 ? n2 : 1, 0);
+  for (int i = 0; i < n1; ++i) {
+    const int m = kf1.map_points[i];
+    mp1[i] = loop_point(mps, geom, m, m >= 0 && mps[m].bad);
+  }
+  for (int i = 0; i < n2; ++i) {
+    const int m = kf2.map_points[i];
+    mp2[i] = loop_point(mps, geom, m, m >= 0 && mps[m].bad);
+  }
+  for (int i = 0; i < n1; ++i) {  // :1116-1126
+    const int m = vpMatches12[i];
+    if (m < 0) continue;
+    already1[i] = 1;
+    for (int o = 0; o < mps[m].n_obs; ++o)  // GetIndexInKeyFrame(pKF2)
+      if (mps[m].obs[o].keyframe == kf2_index) {
+        const int idx2 = mps[m].obs[o].keypoint;
+        if (idx2 >= 0 && idx2 < n2) already2[idx2] = 1;
+        break;
+      }
+  }
+  const slamgpu_kf k1 = loop_kf(kf1, f1), k2 = loop_kf(kf2, f2);
+  std::vector<int32_t> match12(n1 > 0 ? n1 : 1), vn1(n1 > 0 ? n1 : 1), vn2(n2 > 0 ? n2 : 1);
+  int nfound = 0;
+  throw_if(slamgpu_search_by_sim3(&k1, &k2, mp1.data(), mp2.data(), already1.data(),
+                                  already2.data(), s.sR12, s.t12, s.sR21, s.t21, th, &cam, &lv,
+                                  &grid, match12.data(), vn1.data(), vn2.data(), &nfound),
+           slamgpu_loopmatch_last_error);
+  for (int i = 0; i < n1; ++i)
+    if (match12[i] >= 0) vpMatches12[i] = kf2.map_points[match12[i]];
+  return nfound;
 }
 
 }  // namespace slamgpu_adapter

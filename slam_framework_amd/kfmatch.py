@@ -5,6 +5,11 @@ include/slamgpu_kfmatch.h with reference-shaped names.
   fuse                       OrbMatcher::Fuse(pKF, vpMapPoints, th) (orb_matcher.cpp:804-954),
                              the candidate search; fuse_apply is the reference's sequential
                              Replace / AddObservation walk over its result
+and of include/slamgpu_loopmatch.h, the LoopCloser's three Sim3 matchers:
+  search_by_sim3             OrbMatcher::SearchBySim3 (orb_matcher.cpp:1081-1310)
+  search_by_projection_sim3  OrbMatcher::SearchByProjection(pKF, Scw, ...) (:384-497)
+  fuse_sim3                  OrbMatcher::Fuse(pKF, Scw, ...) (:956-1079), the candidate search;
+                             fuse_sim3_apply is the reference's per-point tail (:1061-1075)
 libslamgpu.so is the only compute path (no CPU fallback); errors raise SlamGpuError.
 """
 from __future__ import annotations
@@ -28,7 +33,13 @@ KF_DTYPE = np.dtype([("kps", "<u8"), ("desc", "<u8"), ("u_right", "<u8"), ("has_
                      ("nodes", "<u8"), ("node_start", "<u8"), ("node_feats", "<u8"),
                      ("n", "<i4"), ("n_nodes", "<i4"), ("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)),
                      ("Ow", "<f4", (3,)), ("pad", "<f4")])
+SBP_JOB_DTYPE = np.dtype([("kf", "<i4"), ("pt_begin", "<i4"), ("n_pts", "<i4"),
+                          ("kp_begin", "<i4")])
+SIM3_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("mp1_begin", "<i4"),
+                            ("mp2_begin", "<i4"), ("sR12", "<f4", (9,)), ("t12", "<f4", (3,)),
+                            ("sR21", "<f4", (9,)), ("t21", "<f4", (3,))])
 assert FUSE_POINT_DTYPE.itemsize == 80 and TRI_PAIR_DTYPE.itemsize == 48
+assert SBP_JOB_DTYPE.itemsize == 16 and SIM3_PAIR_DTYPE.itemsize == 112
 assert KF_DTYPE.itemsize == 128
 
 
@@ -95,6 +106,22 @@ def lib():
                                    C.POINTER(Levels), C.POINTER(KfGrid), vp, vp, C.POINTER(ip)]
         L.slamgpu_fuse_device.argtypes = [vp, vp, vp, ip, C.c_float, C.POINTER(G.Camera),
                                           C.POINTER(Levels), C.POINTER(KfGrid), vp, vp, vp]
+        cp, lp, gp, fl = C.POINTER(G.Camera), C.POINTER(Levels), C.POINTER(KfGrid), C.c_float
+        L.slamgpu_loopmatch_last_error.argtypes = []
+        L.slamgpu_loopmatch_last_error.restype = C.c_char_p
+        L.slamgpu_fuse_sim3.argtypes = [C.POINTER(Kf), vp, ip, fl, cp, lp, gp, vp, vp,
+                                        C.POINTER(ip)]
+        L.slamgpu_fuse_sim3_device.argtypes = [vp, ip, vp, ip, vp, fl, cp, lp, gp, vp, vp, vp]
+        L.slamgpu_search_by_projection_sim3.argtypes = [C.POINTER(Kf), vp, ip, vp, fl, cp, lp, gp,
+                                                        vp, vp, C.POINTER(ip)]
+        L.slamgpu_search_by_projection_sim3_scratch_bytes.argtypes = [ip]
+        L.slamgpu_search_by_projection_sim3_scratch_bytes.restype = C.c_size_t
+        L.slamgpu_search_by_projection_sim3_device.argtypes = [
+            vp, vp, ip, vp, ip, ip, vp, ip, fl, cp, lp, gp, vp, vp, vp, vp, C.c_size_t, vp]
+        L.slamgpu_search_by_sim3.argtypes = [C.POINTER(Kf), C.POINTER(Kf), vp, vp, vp, vp, vp, vp,
+                                             vp, vp, fl, cp, lp, gp, vp, vp, vp, C.POINTER(ip)]
+        L.slamgpu_search_by_sim3_device.argtypes = [vp, vp, ip, vp, ip, vp, vp, C.c_int64, fl, cp,
+                                                    lp, gp, vp, vp, vp, vp, vp]
         _bound = True
     return L
 
@@ -219,3 +246,168 @@ def fuse_apply(best_idx, kf_map_points, mp_ids, mp_nobs, mp_bad, mp_in_kf):
             kf_map_points[j] = mid
         nfused += 1
     return nfused
+
+
+# ---- the LoopCloser's Sim3 matchers (include/slamgpu_loopmatch.h) ------------------------------
+TH_HIGH = 100
+SBP_KEEP = 3  # SLAMGPU_SBP_KEEP
+_f32 = np.float32
+
+
+def host_kf_pose(kps, desc, Rcw, tcw, Ow):
+    """A slamgpu_kf over host arrays with the pose blocks given as such (the decomposed Scw of
+    the two Scw calls): no u_right, has_mp or FeatureVector, which the Sim3 matchers never read."""
+    k = np.ascontiguousarray(kps)
+    if len(k) and k.dtype != G.KP_DTYPE:
+        k = k.view(G.KP_DTYPE)
+    d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    s = Kf()
+    s.kps, s.desc, s.n = _p(k), _p(d), len(d)
+    s.Rcw[:] = [float(x) for x in np.asarray(Rcw, np.float32).reshape(-1)]
+    s.tcw[:] = [float(x) for x in np.asarray(tcw, np.float32).reshape(-1)]
+    s.Ow[:] = [float(x) for x in np.asarray(Ow, np.float32).reshape(-1)]
+    return s, [k, d]
+
+
+def decompose_scw(Scw):
+    """Rcw, tcw, Ow of a 4x4 f32 Scw in the reference's operation order (orb_matcher.cpp:393-397,
+    :965-969) under OpenCV's float cv::Mat arithmetic: scw = (float)sqrt(row0 . row0) (Mat::dot,
+    a double sum), Rcw = sRcw / scw and tcw = Scw[:3, 3] / scw as a multiplication by the float
+    1/scw (MatExpr scaling), Ow = -Rcw^T tcw (camera_center). A convenience for Python callers
+    and tests: the C ABI takes the blocks as the caller's own arithmetic made them."""
+    S = np.asarray(Scw, np.float32)
+    r0 = S[0, :3].astype(np.float64)
+    scw = _f32(np.sqrt(float(r0[0] * r0[0]) + float(r0[1] * r0[1]) + float(r0[2] * r0[2])))
+    inv = _f32(1.0 / float(scw))
+    Rcw = (S[:3, :3] * inv).astype(np.float32)
+    tcw = (S[:3, 3] * inv).astype(np.float32)
+    T = np.eye(4, dtype=np.float32)
+    T[:3, :3], T[:3, 3] = Rcw, tcw
+    return Rcw, tcw, camera_center(T)
+
+
+def relative_sim3(s12, R12, t12):
+    """sR12, t12, sR21, t21 as SearchBySim3 computes them (orb_matcher.cpp:1103-1105): sR12 =
+    s12 * R12, sR21 = (1.0 / s12) * R12^T (scalings by a float factor), t21 = -sR21 * t12
+    (OpenCV gemm: float dot products, negated)."""
+    R = np.asarray(R12, np.float32).reshape(3, 3)
+    t = np.asarray(t12, np.float32).reshape(3)
+    s = _f32(s12)
+    sR12 = (R * s).astype(np.float32)
+    sR21 = (R.T * _f32(1.0 / float(s))).astype(np.float32)
+    t21 = np.zeros(3, np.float32)
+    for r in range(3):
+        dot = _f32(_f32(sR21[r, 0] * t[0]) + _f32(sR21[r, 1] * t[1]))
+        t21[r] = -_f32(dot + _f32(sR21[r, 2] * t[2]))
+    return sR12, t.copy(), sR21, t21
+
+
+def fuse_sim3(kf, points, th, cam, lv, grid):
+    """kf: (Kf, keep) from host_kf_pose(decompose_scw(Scw)); points: FUSE_POINT_DTYPE with skip =
+    isBad() or already in the keyframe. Returns (nfused, best_idx, best_dist)."""
+    pts = np.ascontiguousarray(points).view(FUSE_POINT_DTYPE)
+    n = len(pts)
+    bi, bd = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    nf = C.c_int()
+    _check(lib().slamgpu_fuse_sim3(C.byref(kf[0]), _p(pts), n, float(th), C.byref(_cam(cam)),
+                                   C.byref(lv), C.byref(grid), _p(bi), _p(bd), C.byref(nf)))
+    return nf.value, bi[:n], bd[:n]
+
+
+def fuse_sim3_device(d_kfs, n_kfs, d_pts, n_pts, d_skip, th, cam, lv, grid, d_best_idx,
+                     d_best_dist, stream=None):
+    """n_kfs keyframes x one shared point array; d_skip [n_kfs][n_pts] u8 or None; outputs
+    [n_kfs][n_pts]."""
+    from .bow import _dev
+    _check(lib().slamgpu_fuse_sim3_device(
+        _dev(d_kfs), n_kfs, _dev(d_pts), n_pts, _dev(d_skip) if d_skip is not None else None,
+        float(th), C.byref(_cam(cam)), C.byref(lv), C.byref(grid), _dev(d_best_idx),
+        _dev(d_best_dist), C.c_void_p(stream or 0)))
+
+
+def search_by_projection_sim3(kf, points, matched_in, th, cam, lv, grid):
+    """matched_in[idx] = vpMatched[idx] != nullptr at entry. Returns (nmatches, kp_point,
+    point_kp): kp_point[idx] = the point that claimed keypoint idx or -1."""
+    pts = np.ascontiguousarray(points).view(FUSE_POINT_DTYPE)
+    n, m = kf[0].n, len(pts)
+    mi = np.ascontiguousarray(matched_in, np.uint8)
+    if len(mi) != n:
+        raise G.SlamGpuError(f"matched_in has {len(mi)} entries for {n} keypoints")
+    kpp, pkp = np.zeros(max(n, 1), np.int32), np.zeros(max(m, 1), np.int32)
+    nm = C.c_int()
+    _check(lib().slamgpu_search_by_projection_sim3(
+        C.byref(kf[0]), _p(pts), m, _p(mi), float(th), C.byref(_cam(cam)), C.byref(lv),
+        C.byref(grid), _p(kpp), _p(pkp), C.byref(nm)))
+    return nm.value, kpp[:n], pkp[:m]
+
+
+def search_by_projection_sim3_scratch_bytes(n_pts_total):
+    return int(lib().slamgpu_search_by_projection_sim3_scratch_bytes(int(n_pts_total)))
+
+
+def search_by_projection_sim3_device(d_kfs, d_pts, n_pts_total, d_jobs, n_jobs, max_job_pts,
+                                     d_matched_in, n_kp_total, th, cam, lv, grid, d_kp_point,
+                                     d_point_kp, d_nmatches, d_scratch, scratch_bytes,
+                                     stream=None):
+    from .bow import _dev
+    _check(lib().slamgpu_search_by_projection_sim3_device(
+        _dev(d_kfs), _dev(d_pts), n_pts_total, _dev(d_jobs), n_jobs, max_job_pts,
+        _dev(d_matched_in), n_kp_total, float(th), C.byref(_cam(cam)), C.byref(lv), C.byref(grid),
+        _dev(d_kp_point), _dev(d_point_kp), _dev(d_nmatches), _dev(d_scratch), scratch_bytes,
+        C.c_void_p(stream or 0)))
+
+
+def search_by_sim3(kf1, kf2, mp1, mp2, already1, already2, sim3, th, cam, lv, grid):
+    """kf1 / kf2: (Kf, keep) with Rcw / tcw = the keyframes' poses; mp1 / mp2: one
+    FUSE_POINT_DTYPE record per feature (skip = no map point or bad); sim3 = (sR12, t12, sR21,
+    t21) (relative_sim3). Returns (nfound, match12, vn_match1, vn_match2)."""
+    p1 = np.ascontiguousarray(mp1).view(FUSE_POINT_DTYPE)
+    p2 = np.ascontiguousarray(mp2).view(FUSE_POINT_DTYPE)
+    n1, n2 = kf1[0].n, kf2[0].n
+    a1, a2 = np.ascontiguousarray(already1, np.uint8), np.ascontiguousarray(already2, np.uint8)
+    if (len(p1), len(a1), len(p2), len(a2)) != (n1, n1, n2, n2):
+        raise G.SlamGpuError("search_by_sim3: one map point record and one flag per feature")
+    blocks = [np.ascontiguousarray(b, np.float32).reshape(-1) for b in sim3]
+    m12, v1 = np.zeros(max(n1, 1), np.int32), np.zeros(max(n1, 1), np.int32)
+    v2 = np.zeros(max(n2, 1), np.int32)
+    nf = C.c_int()
+    _check(lib().slamgpu_search_by_sim3(
+        C.byref(kf1[0]), C.byref(kf2[0]), _p(p1), _p(p2), _p(a1), _p(a2), _p(blocks[0]),
+        _p(blocks[1]), _p(blocks[2]), _p(blocks[3]), float(th), C.byref(_cam(cam)), C.byref(lv),
+        C.byref(grid), _p(m12), _p(v1), _p(v2), C.byref(nf)))
+    return nf.value, m12[:n1], v1[:n1], v2[:n2]
+
+
+def search_by_sim3_device(d_kfs, d_mp, n_mp_total, d_pairs, n_pairs, d_already1, d_already2,
+                          stride, th, cam, lv, grid, d_match12, d_vn_match1, d_vn_match2,
+                          d_nfound, stream=None):
+    from .bow import _dev
+    _check(lib().slamgpu_search_by_sim3_device(
+        _dev(d_kfs), _dev(d_mp), n_mp_total, _dev(d_pairs), n_pairs, _dev(d_already1),
+        _dev(d_already2), stride, float(th), C.byref(_cam(cam)), C.byref(lv), C.byref(grid),
+        _dev(d_match12), _dev(d_vn_match1), _dev(d_vn_match2), _dev(d_nfound),
+        C.c_void_p(stream or 0)))
+
+
+def fuse_sim3_apply(best_idx, kf_map_points, mp_ids, mp_nobs, mp_bad, mp_in_kf):
+    """The reference's per-point tail of Fuse(pKF, Scw, ...) (orb_matcher.cpp:1061-1075) over the
+    candidate search's result, on an id-based map (arrays as fuse_apply; kf_map_points, mp_nobs
+    and mp_in_kf are mutated). "Bad" and "already in this keyframe" are re-checked here: in a
+    SearchAndFuse batch the Replace calls after an earlier keyframe can have added observations
+    to a loop point since the search ran. Returns (nFused, vpReplacePoint as ids, -1 = none)."""
+    replace = np.full(len(mp_ids), -1, np.int64)
+    nfused = 0
+    for i, mid in enumerate(mp_ids):
+        if mid < 0 or mp_bad[mid] or mp_in_kf[mid] or best_idx[i] < 0:
+            continue
+        j = int(best_idx[i])
+        cur = int(kf_map_points[j])
+        if cur >= 0:
+            if not mp_bad[cur]:
+                replace[i] = cur
+        else:
+            mp_nobs[mid] += 1
+            mp_in_kf[mid] = True
+            kf_map_points[j] = mid
+        nfused += 1
+    return nfused, replace

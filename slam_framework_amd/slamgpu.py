@@ -76,6 +76,11 @@ EXPORTS = [
     # include/slamgpu_kfmatch.h
     "slamgpu_kfmatch_last_error", "slamgpu_search_for_triangulation",
     "slamgpu_search_for_triangulation_device", "slamgpu_fuse", "slamgpu_fuse_device",
+    # include/slamgpu_loopmatch.h
+    "slamgpu_loopmatch_last_error", "slamgpu_fuse_sim3", "slamgpu_fuse_sim3_device",
+    "slamgpu_search_by_projection_sim3", "slamgpu_search_by_projection_sim3_scratch_bytes",
+    "slamgpu_search_by_projection_sim3_device", "slamgpu_search_by_sim3",
+    "slamgpu_search_by_sim3_device",
     # include/slamgpu_io.h
     "slamgpu_io_last_error", "slamgpu_kitti_load_images", "slamgpu_kitti_image_path",
     "slamgpu_png_info", "slamgpu_png_decode", "slamgpu_imread_png",
@@ -613,6 +618,62 @@ class OrbMatcher:
         from . import kfmatch as K
         k = K.host_kf(kf.keypoints, kf.descriptors, kf.u_right, kf.Tcw)
         nf, bi, _ = K.fuse(k, points, th, cam, levels, grid)
+        return nf, bi
+
+    def SearchBySim3(self, kf1, kf2, vpMatches12, s12, R12, t12, th, cam, levels, grid):
+        """SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (orb_matcher.cpp:1081-1310).
+        kf: .keypoints, .descriptors, .Tcw, .map_points (id per feature, -1 = none or bad),
+        .mp_records (one FUSE_POINT record per feature). vpMatches12: kf2 map point id per kf1
+        feature (-1 = none), updated in place where both directions agree. Returns nFound."""
+        from . import kfmatch as K
+        mp1, mp2 = np.asarray(kf1.map_points, np.int64), np.asarray(kf2.map_points, np.int64)
+        m12 = np.asarray(vpMatches12)
+        already1 = m12 >= 0
+        already2 = np.zeros(len(mp2), bool)
+        # GetIndexInKeyFrame(pKF2) of the points already matched (:1116-1126)
+        pos2 = {int(m): i for i, m in enumerate(mp2) if m >= 0}
+        for m in m12[already1]:
+            if int(m) in pos2:
+                already2[pos2[int(m)]] = True
+
+        def host(kf):
+            T = np.asarray(kf.Tcw, np.float32)
+            return K.host_kf_pose(kf.keypoints, kf.descriptors, T[:3, :3], T[:3, 3],
+                                  K.camera_center(T))
+
+        def records(kf, mps):
+            r = np.ascontiguousarray(kf.mp_records).view(K.FUSE_POINT_DTYPE).copy()
+            r["skip"] = (r["skip"] != 0) | (mps < 0)
+            return r
+        nf, match12, _, _ = K.search_by_sim3(host(kf1), host(kf2), records(kf1, mp1),
+                                             records(kf2, mp2), already1, already2,
+                                             K.relative_sim3(s12, R12, t12), th, cam, levels, grid)
+        sel = match12 >= 0
+        vpMatches12[sel] = mp2[match12[sel]]
+        return nf
+
+    def SearchByProjectionSim3(self, kf, Scw, points, vpMatched, th, cam, levels, grid,
+                               point_ids=None):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (orb_matcher.cpp:384-497).
+        points: FUSE_POINT records (skip = isBad() or already in vpMatched); vpMatched: map point
+        id per keypoint (-1 = none), updated in place with point_ids[i] (default i) of the
+        claiming point. Returns nmatches."""
+        from . import kfmatch as K
+        k = K.host_kf_pose(kf.keypoints, kf.descriptors, *K.decompose_scw(Scw))
+        nm, kp_point, _ = K.search_by_projection_sim3(k, points, np.asarray(vpMatched) >= 0, th,
+                                                      cam, levels, grid)
+        sel = kp_point >= 0
+        ids = np.arange(len(points)) if point_ids is None else np.asarray(point_ids)
+        vpMatched[sel] = ids[kp_point[sel]]
+        return nm
+
+    def FuseSim3(self, kf, Scw, points, th, cam, levels, grid):
+        """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (orb_matcher.cpp:956-1079): the per-point
+        candidate search on the device; returns (nfused, best_idx) -- kfmatch.fuse_sim3_apply
+        does the reference's tail (vpReplacePoint / AddObservation) over it."""
+        from . import kfmatch as K
+        k = K.host_kf_pose(kf.keypoints, kf.descriptors, *K.decompose_scw(Scw))
+        nf, bi, _ = K.fuse_sim3(k, points, th, cam, levels, grid)
         return nf, bi
 
 
