@@ -14,9 +14,14 @@
  *   cv::cvtColor(CV_{RGB,BGR,RGBA,BGRA}2GRAY) of Tracker::GrabImageStereo  tracker.cpp:110-127
  * Conventions as slamgpu.h: POD types, caller-owned buffers, 0 or a negative SLAMGPU_E* code with
  * the message in slamgpu_bow_last_error() (per thread). Synchronous host-buffer calls stage
- * through device buffers owned by the vocabulary (transform) or by the calling thread (the
- * others); the *_device calls take device pointers and a hipStream_t, never allocate and return
- * without synchronising.
+ * through the calling thread's device buffer and stream (one per thread, shared with the
+ * synchronous calls of slamgpu_optimizer.h, slamgpu_kfmatch.h and slamgpu_loopmatch.h; kept until
+ * the process ends) and return after synchronising; the *_device calls take device pointers and a
+ * hipStream_t, never allocate and return without synchronising.
+ * A slamgpu_vocab holds only read-only device tables once created: any number of threads may
+ * call slamgpu_bow_transform on one vocabulary at the same time (the reference's tracking and
+ * local-mapping threads both call ComputeBoW on the one ORBVocabulary); transform runs on the
+ * vocabulary's device, on the calling thread's stream.
  */
 #ifndef SLAMGPU_BOW_H_
 #define SLAMGPU_BOW_H_

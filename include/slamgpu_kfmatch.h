@@ -10,7 +10,7 @@
  *     caller LocalMapper::SearchInNeighbors
  * Conventions as slamgpu.h: POD types, caller-owned buffers, 0 or a negative SLAMGPU_E* code
  * with the message in slamgpu_kfmatch_last_error() (per thread). The synchronous calls stage
- * through per-thread device buffers; the *_device calls take device pointers and a hipStream_t,
+ * through the calling thread's device buffer (see slamgpu_bow.h); the *_device calls take device pointers and a hipStream_t,
  * never allocate and return without synchronising.
  */
 #ifndef SLAMGPU_KFMATCH_H_

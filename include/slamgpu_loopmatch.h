@@ -20,7 +20,7 @@
  * slamgpu_kf_grid and slamgpu_camera are reused: POD types, caller-owned buffers, 0 or a negative
  * SLAMGPU_E* code with the message in slamgpu_loopmatch_last_error() (per thread; the same
  * string slamgpu_kfmatch_last_error() returns). The synchronous calls take host pointers and
- * stage through per-thread device buffers; the *_device calls take device pointers and a
+ * stage through the calling thread's device buffer; the *_device calls take device pointers and a
  * hipStream_t, never allocate and return without synchronising. n <= SLAMGPU_KF_MAX_FEATURES
  * per keyframe (the synchronous calls reject more; a *_device call flags the job, see below).
  * A keypoint whose octave is outside [0, 255) never matches in a *_device call.

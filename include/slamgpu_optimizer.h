@@ -14,6 +14,8 @@
  *   slamgpu_optimize_essential_graph  Optimizer::OptimizeEssentialGraph    optimizer.cpp:718-960
  * These calls hold no state, so they take no handle. Every function returns 0 or a negative
  * SLAMGPU_E* code (slamgpu.h) with a message in slamgpu_optimizer_last_error() (per thread).
+ * The synchronous calls stage through the calling thread's device buffer and stream (one per
+ * thread, shared with the other headers' synchronous calls, see slamgpu_bow.h).
  *
  * Arithmetic is FP64 on the device, with the reference's f32 inputs and f32 quirks (stereo
  * cam_project's float inverse depth, the f32 chi2 threshold tests, the f32 pose output); the

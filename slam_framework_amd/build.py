@@ -39,6 +39,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_capi_check()
         build_adapter_check()
         build_geometry_check()
+        build_host_stage_check()
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -66,6 +67,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_capi_check()
     build_adapter_check()
     build_geometry_check()
+    build_host_stage_check()
     return LIB
 
 
@@ -127,6 +129,29 @@ def build_geometry_check() -> str:
                    check=True)
     os.replace(tmp, GEOMETRY_BIN)
     return GEOMETRY_BIN
+
+
+HOST_STAGE_SRC = os.path.join(ROOT, "tests", "host_stage_check.cpp")
+HOST_STAGE_BIN = os.path.join(ROOT, "tests", "host_stage_check")
+
+
+def build_host_stage_check() -> str:
+    """g++ build of tests/host_stage_check.cpp with the address and undefined-behaviour
+    sanitizers: csrc/stage_layout.h (the staging layouts of every synchronous wrapper and the
+    FeatureVector validator, HIP-free) walked on the CPU, no libslamgpu.so. The sanitizer
+    runtimes are linked statically: the program runs as it is, whatever else is preloaded."""
+    deps = [HOST_STAGE_SRC, os.path.join(CSRC, "stage_layout.h"),
+            os.path.join(CSRC, "host_common.h")] + glob.glob(os.path.join(ROOT, "include", "*.h"))
+    if os.path.exists(HOST_STAGE_BIN) and os.path.getmtime(HOST_STAGE_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return HOST_STAGE_BIN
+    tmp = HOST_STAGE_BIN + ".tmp"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-static-libasan", "-static-libubsan", "-I", CSRC,
+                    HOST_STAGE_SRC, "-o", tmp], check=True)
+    os.replace(tmp, HOST_STAGE_BIN)
+    return HOST_STAGE_BIN
 
 
 if __name__ == "__main__":

@@ -15,7 +15,6 @@
 
 #include <algorithm>
 #include <cerrno>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,20 +22,11 @@
 #include <vector>
 
 #include "../../include/slamgpu_io.h"
+#include "host_common.h"
+
+using slamgpu::t_io_err;
 
 namespace {
-
-thread_local std::string t_err;
-
-int fail(int rc, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  std::vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  t_err = buf;
-  return rc;
-}
 
 // A chunk type for messages: its four letters, or hex when they are not printable ASCII.
 std::string chunk_name(const uint8_t* t) {
@@ -65,45 +55,45 @@ struct Png {
 int parse(const uint8_t* d, size_t n, Png* p, bool headers_only) {
   static const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
   if (!d || n < 8 + 25 || std::memcmp(d, sig, 8) != 0)
-    return fail(SLAMGPU_EINVAL, "not a PNG file");
+    return t_io_err.fail(SLAMGPU_EINVAL, "not a PNG file");
   size_t off = 8;
   bool have_ihdr = false, have_iend = false;
   while (off + 12 <= n) {
     const uint32_t len = be32(d + off);
     const uint8_t* type = d + off + 4;
     const uint8_t* body = d + off + 8;
-    if (len > n - off - 12) return fail(SLAMGPU_EINVAL, "PNG chunk overruns the file");
+    if (len > n - off - 12) return t_io_err.fail(SLAMGPU_EINVAL, "PNG chunk overruns the file");
     const uint32_t crc = be32(body + len);
     if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), type, len + 4) != crc)
-      return fail(SLAMGPU_EINVAL, "PNG chunk %s: CRC mismatch", chunk_name(type).c_str());
+      return t_io_err.fail(SLAMGPU_EINVAL, "PNG chunk %s: CRC mismatch", chunk_name(type).c_str());
     if (!have_ihdr) {
       if (std::memcmp(type, "IHDR", 4) != 0 || len != 13)
-        return fail(SLAMGPU_EINVAL, "PNG: IHDR is not the first chunk");
+        return t_io_err.fail(SLAMGPU_EINVAL, "PNG: IHDR is not the first chunk");
       p->w = be32(body);
       p->h = be32(body + 4);
       p->depth = body[8];
       p->color = body[9];
       p->interlace = body[12];
       if (body[10] != 0 || body[11] != 0 || p->interlace > 1)
-        return fail(SLAMGPU_EINVAL, "PNG: unknown compression / filter / interlace method");
+        return t_io_err.fail(SLAMGPU_EINVAL, "PNG: unknown compression / filter / interlace method");
       if (p->w == 0 || p->h == 0 || p->w > (1u << 24) || p->h > (1u << 24))
-        return fail(SLAMGPU_EINVAL, "PNG: bad size %ux%u", p->w, p->h);
+        return t_io_err.fail(SLAMGPU_EINVAL, "PNG: bad size %ux%u", p->w, p->h);
       switch (p->color) {
         case 0: p->samples = 1; p->out_channels = 1; break;  // gray
         case 2: p->samples = 3; p->out_channels = 3; break;  // RGB
         case 3: p->samples = 1; p->out_channels = 3; break;  // palette
         case 4: p->samples = 2; p->out_channels = 4; break;  // gray + alpha -> BGRA
         case 6: p->samples = 4; p->out_channels = 4; break;  // RGBA
-        default: return fail(SLAMGPU_EINVAL, "PNG: colour type %d", p->color);
+        default: return t_io_err.fail(SLAMGPU_EINVAL, "PNG: colour type %d", p->color);
       }
       const bool ok_depth = p->depth == 8 || ((p->color == 0 || p->color == 3) &&
                                               (p->depth == 1 || p->depth == 2 || p->depth == 4));
       if (!ok_depth)
-        return fail(SLAMGPU_EINVAL, "PNG: %d-bit samples of colour type %d are not supported "
+        return t_io_err.fail(SLAMGPU_EINVAL, "PNG: %d-bit samples of colour type %d are not supported "
                     "(8-bit images only)", p->depth, p->color);
       have_ihdr = true;
     } else if (std::memcmp(type, "PLTE", 4) == 0) {
-      if (len % 3 || len > 768) return fail(SLAMGPU_EINVAL, "PNG: bad PLTE");
+      if (len % 3 || len > 768) return t_io_err.fail(SLAMGPU_EINVAL, "PNG: bad PLTE");
       p->plte.assign(body, body + len);
     } else if (std::memcmp(type, "tRNS", 4) == 0) {
       if (p->color == 3) p->trns.assign(body, body + len);
@@ -113,16 +103,16 @@ int parse(const uint8_t* d, size_t n, Png* p, bool headers_only) {
       have_iend = true;
       break;
     } else if (!(type[0] & 0x20)) {
-      return fail(SLAMGPU_EINVAL, "PNG: unknown critical chunk %s", chunk_name(type).c_str());
+      return t_io_err.fail(SLAMGPU_EINVAL, "PNG: unknown critical chunk %s", chunk_name(type).c_str());
     }
     off += 12 + (size_t)len;
   }
-  if (!have_ihdr) return fail(SLAMGPU_EINVAL, "PNG: no IHDR");
+  if (!have_ihdr) return t_io_err.fail(SLAMGPU_EINVAL, "PNG: no IHDR");
   if (p->color == 3) {
-    if (p->plte.empty()) return fail(SLAMGPU_EINVAL, "PNG: palette image without PLTE");
+    if (p->plte.empty()) return t_io_err.fail(SLAMGPU_EINVAL, "PNG: palette image without PLTE");
     if (!p->trns.empty()) p->out_channels = 4;
   }
-  if (!headers_only && !have_iend) return fail(SLAMGPU_EINVAL, "PNG: truncated (no IEND)");
+  if (!headers_only && !have_iend) return t_io_err.fail(SLAMGPU_EINVAL, "PNG: truncated (no IEND)");
   return 0;
 }
 
@@ -153,7 +143,7 @@ int unfilter(const uint8_t* in, size_t rows, size_t rowbytes, int bpp, std::vect
         case 2: v += b; break;
         case 3: v += (a + b) >> 1; break;
         case 4: v += paeth(a, b, c); break;
-        default: return fail(SLAMGPU_EINVAL, "PNG: row filter %d", f);
+        default: return t_io_err.fail(SLAMGPU_EINVAL, "PNG: row filter %d", f);
       }
       cur[x] = (uint8_t)v;
     }
@@ -216,7 +206,7 @@ int decode(const uint8_t* data, size_t size, uint8_t* out, size_t pitch, size_t 
   const size_t row_out = (size_t)p.w * p.out_channels;
   if (!out) return 0;
   if (pitch < row_out || cap < pitch * (p.h - 1) + row_out)
-    return fail(SLAMGPU_ECAP, "PNG %ux%ux%d: output buffer too small", p.w, p.h,
+    return t_io_err.fail(SLAMGPU_ECAP, "PNG %ux%ux%d: output buffer too small", p.w, p.h,
                 p.out_channels);
   const int bits_pp = p.samples * p.depth, bpp = bits_pp >= 8 ? bits_pp / 8 : 1;
   // Adam7 passes (x0, y0, dx, dy); a single full pass when not interlaced
@@ -236,7 +226,7 @@ int decode(const uint8_t* data, size_t size, uint8_t* out, size_t pitch, size_t 
   uLongf got = (uLongf)raw_size;
   const int zr = uncompress(raw.data(), &got, p.idat.data(), (uLong)p.idat.size());
   if (zr != Z_OK || got != raw_size)
-    return fail(SLAMGPU_EINVAL, "PNG: image data does not inflate to %zu bytes (zlib %d)",
+    return t_io_err.fail(SLAMGPU_EINVAL, "PNG: image data does not inflate to %zu bytes (zlib %d)",
                 raw_size, zr);
   size_t off = 0;
   std::vector<uint8_t> rows;
@@ -272,15 +262,15 @@ bool read_file(const char* path, std::vector<uint8_t>* buf) {
 
 extern "C" {
 
-const char* slamgpu_io_last_error(void) { return t_err.c_str(); }
+const char* slamgpu_io_last_error(void) { return t_io_err.c_str(); }
 
 int slamgpu_kitti_load_images(const char* kitti_path, double* timestamps, int cap,
                               int* n_frames) {
-  if (!kitti_path || !n_frames || cap < 0) return fail(SLAMGPU_EINVAL, "bad arguments");
+  if (!kitti_path || !n_frames || cap < 0) return t_io_err.fail(SLAMGPU_EINVAL, "bad arguments");
   *n_frames = 0;
   const std::string file = std::string(kitti_path) + "/times.txt";
   FILE* f = std::fopen(file.c_str(), "r");
-  if (!f) return fail(SLAMGPU_EINVAL, "Error opening %s", file.c_str());
+  if (!f) return t_io_err.fail(SLAMGPU_EINVAL, "Error opening %s", file.c_str());
   char line[256];
   int n = 0;
   while (std::fgets(line, sizeof(line), f)) {
@@ -294,7 +284,7 @@ int slamgpu_kitti_load_images(const char* kitti_path, double* timestamps, int ca
     const double t = std::strtod(line, &end);
     if (end == line || errno == ERANGE) {
       std::fclose(f);
-      return fail(SLAMGPU_EINVAL, "%s: line %d is not a number", file.c_str(), n + 1);
+      return t_io_err.fail(SLAMGPU_EINVAL, "%s: line %d is not a number", file.c_str(), n + 1);
     }
     if (timestamps && n < cap) timestamps[n] = t;
     n++;
@@ -307,9 +297,9 @@ int slamgpu_kitti_load_images(const char* kitti_path, double* timestamps, int ca
 int slamgpu_kitti_image_path(const char* kitti_path, int camera, int index, char* out,
                              size_t cap) {
   if (!kitti_path || !out || index < 0 || camera < 0 || camera > 9)
-    return fail(SLAMGPU_EINVAL, "bad arguments");
+    return t_io_err.fail(SLAMGPU_EINVAL, "bad arguments");
   const int n = std::snprintf(out, cap, "%s/image_%d/%06d.png", kitti_path, camera, index);
-  if (n < 0 || (size_t)n >= cap) return fail(SLAMGPU_ECAP, "path needs %d bytes", n + 1);
+  if (n < 0 || (size_t)n >= cap) return t_io_err.fail(SLAMGPU_ECAP, "path needs %d bytes", n + 1);
   return 0;
 }
 
@@ -324,14 +314,14 @@ int slamgpu_png_info(const uint8_t* data, size_t size, int* width, int* height, 
 
 int slamgpu_png_decode(const uint8_t* data, size_t size, uint8_t* out, size_t out_pitch,
                        size_t out_cap, int* width, int* height, int* channels) {
-  if (!out) return fail(SLAMGPU_EINVAL, "png_decode: no output buffer");
+  if (!out) return t_io_err.fail(SLAMGPU_EINVAL, "png_decode: no output buffer");
   return decode(data, size, out, out_pitch, out_cap, width, height, channels);
 }
 
 int slamgpu_imread_png(const char* path, uint8_t* out, size_t out_pitch, size_t out_cap,
                        int* width, int* height, int* channels) {
   std::vector<uint8_t> buf;
-  if (!path || !read_file(path, &buf)) return fail(SLAMGPU_EINVAL, "cannot read %s", path ? path : "");
+  if (!path || !read_file(path, &buf)) return t_io_err.fail(SLAMGPU_EINVAL, "cannot read %s", path ? path : "");
   if (!out) return slamgpu_png_info(buf.data(), buf.size(), width, height, channels);
   return decode(buf.data(), buf.size(), out, out_pitch, out_cap, width, height, channels);
 }

@@ -273,7 +273,7 @@ using namespace slamgpu;
 
 extern "C" {
 
-const char* slamgpu_kfmatch_last_error(void) { return t_err.c_str(); }
+const char* slamgpu_kfmatch_last_error(void) { return t_kf_err.c_str(); }
 
 int slamgpu_search_for_triangulation_device(const slamgpu_kf* d_kfs,
                                             const slamgpu_tri_pair* d_pairs, int n_pairs,
@@ -281,15 +281,15 @@ int slamgpu_search_for_triangulation_device(const slamgpu_kf* d_kfs,
                                             int check_ori, int32_t* d_match12,
                                             int64_t match_stride, int32_t* d_nmatches,
                                             void* stream) {
-  if (n_pairs < 0) return fail(SLAMGPU_EINVAL, "n_pairs %d < 0", n_pairs);
+  if (n_pairs < 0) return t_kf_err.fail(SLAMGPU_EINVAL, "n_pairs %d < 0", n_pairs);
   if (n_pairs == 0) return 0;
   if (!d_kfs || !d_pairs || !d_match12 || !d_nmatches || !cam)
-    return fail(SLAMGPU_EINVAL, "NULL argument");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
   if (int r = check_levels(lv)) return r;
   hipLaunchKernelGGL(search_tri_kernel, dim3(n_pairs), dim3(64 * kTriWaves), 0,
                      static_cast<hipStream_t>(stream), d_kfs, d_pairs, *cam, *lv,
                      check_ori ? 1 : 0, d_match12, match_stride, d_nmatches);
-  KF_HIPCHECK(hipGetLastError());
+  HIPCHECK(t_kf_err, hipGetLastError());
   return 0;
 }
 
@@ -301,36 +301,31 @@ int slamgpu_search_for_triangulation(const slamgpu_kf* kf1, const slamgpu_kf* kf
   if (int r = check_kf(kf2, true, "kf2")) return r;
   if (int r = check_levels(lv)) return r;
   if (!F12 || !cam || !nmatches || (kf1->n > 0 && !match12))
-    return fail(SLAMGPU_EINVAL, "NULL argument");
-  size_t need = kf_bytes(*kf1, true) + kf_bytes(*kf2, true) + al256(2 * sizeof(slamgpu_kf)) +
-                al256(sizeof(slamgpu_tri_pair)) + al256((size_t)kf1->n * 4 + 4) + al256(4);
-  if (int r = stage_reserve(need)) return r;
-  size_t off = 0;
-  slamgpu_kf dk[2] = {stage_kf(*kf1, true, &off), stage_kf(*kf2, true, &off)};
-  char* base = t_stage.buf;
-  hipStream_t st = t_stage.stream;
-  slamgpu_kf* d_kfs = reinterpret_cast<slamgpu_kf*>(base + off);
-  off += al256(sizeof(dk));
+    return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
+  StageLease S(t_kf_err);
+  StageLayout L;
+  const int n[2] = {kf1->n, kf2->n}, n_nodes[2] = {kf1->n_nodes, kf2->n_nodes};
+  const int n_feats[2] = {n_nodes[0] > 0 ? kf1->node_start[n_nodes[0]] : 0,
+                          n_nodes[1] > 0 ? kf2->node_start[n_nodes[1]] : 0};
+  const TriLayout t = layout_search_tri(L, n, n_nodes, n_feats);
+  if (int r = S.reserve(L.size())) return r;
+  hipStream_t st = S.stream();
+  const slamgpu_kf dk[2] = {upload_kf(S, *kf1, t.kf[0]), upload_kf(S, *kf2, t.kf[1])};
   slamgpu_tri_pair pr{};
   pr.kf1 = 0;
   pr.kf2 = 1;
   for (int i = 0; i < 9; i++) pr.F12[i] = F12[i];
   pr.only_stereo = only_stereo ? 1 : 0;
-  slamgpu_tri_pair* d_pair = reinterpret_cast<slamgpu_tri_pair*>(base + off);
-  off += al256(sizeof(pr));
-  int32_t* d_match = reinterpret_cast<int32_t*>(base + off);
-  off += al256((size_t)kf1->n * 4 + 4);
-  int32_t* d_nm = reinterpret_cast<int32_t*>(base + off);
-  KF_HIPCHECK(hipMemcpyAsync(d_kfs, dk, sizeof(dk), hipMemcpyHostToDevice, st));
-  KF_HIPCHECK(hipMemcpyAsync(d_pair, &pr, sizeof(pr), hipMemcpyHostToDevice, st));
-  if (int r = slamgpu_search_for_triangulation_device(d_kfs, d_pair, 1, cam, lv, check_ori,
-                                                      d_match, 0, d_nm, st))
+  HIPCHECK(t_kf_err, S.upload(t.kfs, dk, sizeof(dk)));
+  HIPCHECK(t_kf_err, S.upload(t.pair, &pr, sizeof(pr)));
+  if (int r = slamgpu_search_for_triangulation_device(
+          S.at<slamgpu_kf>(t.kfs), S.at<slamgpu_tri_pair>(t.pair), 1, cam, lv, check_ori,
+          S.at<int32_t>(t.match), 0, S.at<int32_t>(t.nmatches), st))
     return r;
   int32_t nm = 0;
-  KF_HIPCHECK(hipMemcpyAsync(&nm, d_nm, 4, hipMemcpyDeviceToHost, st));
-  if (kf1->n > 0)
-    KF_HIPCHECK(hipMemcpyAsync(match12, d_match, (size_t)kf1->n * 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipStreamSynchronize(st));
+  HIPCHECK(t_kf_err, S.download(&nm, t.nmatches, 4));
+  HIPCHECK(t_kf_err, S.download(match12, t.match, (size_t)kf1->n * 4));
+  HIPCHECK(t_kf_err, hipStreamSynchronize(st));
   *nmatches = nm;
   return 0;
 }
@@ -340,16 +335,16 @@ int slamgpu_fuse_device(const slamgpu_kf* d_kfs, const slamgpu_fuse_point* d_pts
                         const slamgpu_camera* cam, const slamgpu_levels* lv,
                         const slamgpu_kf_grid* grid, int32_t* d_best_idx, int32_t* d_best_dist,
                         void* stream) {
-  if (n_pts < 0) return fail(SLAMGPU_EINVAL, "n_pts %d < 0", n_pts);
+  if (n_pts < 0) return t_kf_err.fail(SLAMGPU_EINVAL, "n_pts %d < 0", n_pts);
   if (n_pts == 0) return 0;
   if (!d_kfs || !d_pts || !d_best_idx || !d_best_dist || !cam || !grid)
-    return fail(SLAMGPU_EINVAL, "NULL argument");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
   if (int r = check_levels(lv)) return r;
-  if (!(grid->cell_w > 0) || !(grid->cell_h > 0)) return fail(SLAMGPU_EINVAL, "grid cell size");
+  if (int r = check_grid(grid)) return r;
   hipLaunchKernelGGL(fuse_kernel, dim3((n_pts + 3) / 4), dim3(256), 0,
                      static_cast<hipStream_t>(stream), d_kfs, d_pts, d_point_kf, n_pts, th, *cam,
                      *lv, *grid, d_best_idx, d_best_dist);
-  KF_HIPCHECK(hipGetLastError());
+  HIPCHECK(t_kf_err, hipGetLastError());
   return 0;
 }
 
@@ -359,35 +354,27 @@ int slamgpu_fuse(const slamgpu_kf* kf, const slamgpu_fuse_point* pts, int n_pts,
   if (int r = check_kf(kf, false, "kf")) return r;
   if (int r = check_levels(lv)) return r;
   if (n_pts < 0 || !cam || !grid || !nfused || (n_pts > 0 && (!pts || !best_idx || !best_dist)))
-    return fail(SLAMGPU_EINVAL, "bad arguments");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "bad arguments");
   for (int j = 0; j < kf->n; j++)
     if (kf->kps[j].octave >= lv->nlevels)
-      return fail(SLAMGPU_EINVAL, "keypoint %d octave %d >= nlevels", j, kf->kps[j].octave);
+      return t_kf_err.fail(SLAMGPU_EINVAL, "keypoint %d octave %d >= nlevels", j, kf->kps[j].octave);
   *nfused = 0;
   if (n_pts == 0) return 0;
-  const size_t need = kf_bytes(*kf, false) + al256(sizeof(slamgpu_kf)) +
-                      al256((size_t)n_pts * sizeof(slamgpu_fuse_point)) + 2 * al256((size_t)n_pts * 4);
-  if (int r = stage_reserve(need)) return r;
-  size_t off = 0;
-  const slamgpu_kf dk = stage_kf(*kf, false, &off);
-  char* base = t_stage.buf;
-  hipStream_t st = t_stage.stream;
-  slamgpu_kf* d_kf = reinterpret_cast<slamgpu_kf*>(base + off);
-  off += al256(sizeof(dk));
-  slamgpu_fuse_point* d_pts = reinterpret_cast<slamgpu_fuse_point*>(base + off);
-  off += al256((size_t)n_pts * sizeof(slamgpu_fuse_point));
-  int32_t* d_idx = reinterpret_cast<int32_t*>(base + off);
-  off += al256((size_t)n_pts * 4);
-  int32_t* d_dist = reinterpret_cast<int32_t*>(base + off);
-  KF_HIPCHECK(hipMemcpyAsync(d_kf, &dk, sizeof(dk), hipMemcpyHostToDevice, st));
-  KF_HIPCHECK(hipMemcpyAsync(d_pts, pts, (size_t)n_pts * sizeof(slamgpu_fuse_point),
-                             hipMemcpyHostToDevice, st));
-  if (int r = slamgpu_fuse_device(d_kf, d_pts, nullptr, n_pts, th, cam, lv, grid, d_idx, d_dist,
-                                  st))
+  StageLease S(t_kf_err);
+  StageLayout L;
+  const FuseLayout f = layout_fuse(L, kKfStereo, kf->n, n_pts);
+  if (int r = S.reserve(L.size())) return r;
+  hipStream_t st = S.stream();
+  const slamgpu_kf dk = upload_kf(S, *kf, f.kf);
+  HIPCHECK(t_kf_err, S.upload(f.kfs, &dk, sizeof(dk)));
+  HIPCHECK(t_kf_err, S.upload(f.pts, pts, (size_t)n_pts * sizeof(slamgpu_fuse_point)));
+  if (int r = slamgpu_fuse_device(S.at<slamgpu_kf>(f.kfs), S.at<slamgpu_fuse_point>(f.pts), nullptr,
+                                  n_pts, th, cam, lv, grid, S.at<int32_t>(f.best_idx),
+                                  S.at<int32_t>(f.best_dist), st))
     return r;
-  KF_HIPCHECK(hipMemcpyAsync(best_idx, d_idx, (size_t)n_pts * 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipMemcpyAsync(best_dist, d_dist, (size_t)n_pts * 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipStreamSynchronize(st));
+  HIPCHECK(t_kf_err, S.download(best_idx, f.best_idx, (size_t)n_pts * 4));
+  HIPCHECK(t_kf_err, S.download(best_dist, f.best_dist, (size_t)n_pts * 4));
+  HIPCHECK(t_kf_err, hipStreamSynchronize(st));
   int nf = 0;
   for (int i = 0; i < n_pts; i++) nf += best_idx[i] >= 0;
   *nfused = nf;

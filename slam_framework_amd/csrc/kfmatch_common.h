@@ -1,17 +1,15 @@
 // kfmatch_common.h -- what kfmatch.hip (LocalMapper matchers) and loopmatch.hip (LoopCloser
 // matchers) share: the descriptor distance, OpenCV's small gemm row, the KeyFrame grid-window
-// arithmetic of GetFeaturesInArea, and the host side of the synchronous calls (per-thread error
-// string, staging buffer + stream, keyframe validation and upload).
+// arithmetic of GetFeaturesInArea, and the host side of a keyframe: its validation and its place in
+// and upload to the staging buffer (host_stage.h; errors go to t_kf_err).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdarg>
-#include <cstdio>
-#include <string>
-
 #include "../../include/slamgpu_kfmatch.h"
 #include "device_math.h"
+#include "host_stage.h"
+#include "stage_layout.h"
 
 namespace slamgpu {
 
@@ -54,134 +52,60 @@ __device__ __forceinline__ void kp_cell(float x, float y, const slamgpu_kf_grid&
   *py = (int)roundf((y - g.min_y) / g.cell_h);
 }
 
-inline thread_local std::string t_err;
-
-inline int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  t_err = buf;
-  return code;
-}
-
-#define KF_HIPCHECK(x)                                                                  \
-  do {                                                                                  \
-    hipError_t e_ = (x);                                                                \
-    if (e_ != hipSuccess) return fail(SLAMGPU_EHIP, "%s failed: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
-inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-
-// Per-thread staging buffer + stream of the synchronous calls.
-struct Stage {
-  int device = -1;
-  hipStream_t stream = nullptr;
-  char* buf = nullptr;
-  size_t bytes = 0;
-  ~Stage() {
-    if (buf) (void)hipFree(buf);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-inline thread_local Stage t_stage;
-
-inline int stage_reserve(size_t need) {
-  Stage& S = t_stage;
-  int dev = 0;
-  KF_HIPCHECK(hipGetDevice(&dev));
-  if (S.device != dev) {
-    if (S.buf) (void)hipFree(S.buf);
-    if (S.stream) (void)hipStreamDestroy(S.stream);
-    S.buf = nullptr;
-    S.stream = nullptr;
-    S.bytes = 0;
-    KF_HIPCHECK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-    S.device = dev;
-  }
-  if (need > S.bytes) {
-    if (S.buf) KF_HIPCHECK(hipFree(S.buf));
-    S.buf = nullptr;
-    S.bytes = 0;
-    const size_t cap = need < (1u << 20) ? (1u << 20) : need;
-    KF_HIPCHECK(hipMalloc(&S.buf, cap));
-    S.bytes = cap;
-  }
+inline int check_levels(const slamgpu_levels* lv) {
+  if (!lv || lv->nlevels < 1 || lv->nlevels > 32)
+    return t_kf_err.fail(SLAMGPU_EINVAL, "levels: nlevels outside [1, 32]");
   return 0;
 }
 
-inline int check_levels(const slamgpu_levels* lv) {
-  if (!lv || lv->nlevels < 1 || lv->nlevels > 32)
-    return fail(SLAMGPU_EINVAL, "levels: nlevels outside [1, 32]");
+inline int check_grid(const slamgpu_kf_grid* grid) {
+  if (!(grid->cell_w > 0) || !(grid->cell_h > 0))
+    return t_kf_err.fail(SLAMGPU_EINVAL, "grid cell size");
   return 0;
 }
 
 inline int check_kf(const slamgpu_kf* k, bool fv, const char* name) {
-  if (!k) return fail(SLAMGPU_EINVAL, "%s is NULL", name);
+  if (!k) return t_kf_err.fail(SLAMGPU_EINVAL, "%s is NULL", name);
   if (k->n < 0 || k->n > kMaxFeat)
-    return fail(SLAMGPU_EINVAL, "%s: n %d outside [0, %d]", name, k->n, kMaxFeat);
+    return t_kf_err.fail(SLAMGPU_EINVAL, "%s: n %d outside [0, %d]", name, k->n, kMaxFeat);
   if (k->n > 0 && (!k->kps || !k->desc || !k->u_right || (fv && !k->has_mp)))
-    return fail(SLAMGPU_EINVAL, "%s: NULL keypoint arrays", name);
+    return t_kf_err.fail(SLAMGPU_EINVAL, "%s: NULL keypoint arrays", name);
   if (fv) {
     if (k->n_nodes < 0 || k->n_nodes > k->n)
-      return fail(SLAMGPU_EINVAL, "%s: n_nodes %d outside [0, n]", name, k->n_nodes);
-    if (k->n_nodes > 0) {
-      if (!k->nodes || !k->node_start || !k->node_feats)
-        return fail(SLAMGPU_EINVAL, "%s: NULL FeatureVector", name);
-      if (k->node_start[0] != 0) return fail(SLAMGPU_EINVAL, "%s: node_start[0] != 0", name);
-      for (int i = 0; i < k->n_nodes; i++) {
-        if (k->node_start[i + 1] < k->node_start[i] || k->node_start[i + 1] > k->n)
-          return fail(SLAMGPU_EINVAL, "%s: node_start not ascending within [0, n]", name);
-        if (i > 0 && k->nodes[i] <= k->nodes[i - 1])
-          return fail(SLAMGPU_EINVAL, "%s: nodes not strictly ascending", name);
-      }
-      for (int j = 0; j < k->node_start[k->n_nodes]; j++)
-        if (k->node_feats[j] >= (uint32_t)k->n)
-          return fail(SLAMGPU_EINVAL, "%s: feature index >= n", name);
-    }
+      return t_kf_err.fail(SLAMGPU_EINVAL, "%s: n_nodes %d outside [0, n]", name, k->n_nodes);
+    if (k->n_nodes > 0)
+      if (int r = check_feature_vector(t_kf_err, name, k->n, k->n_nodes, k->nodes, k->node_start,
+                                       k->node_feats, "%s: feature index >= n"))
+        return r;
   }
   for (int j = 0; j < k->n; j++)
     if (k->kps[j].octave < 0 || k->kps[j].octave >= 32)
-      return fail(SLAMGPU_EINVAL, "%s: keypoint %d octave %d outside [0, 32)", name, j,
-                  k->kps[j].octave);
+      return t_kf_err.fail(SLAMGPU_EINVAL, "%s: keypoint %d octave %d outside [0, 32)", name, j,
+                           k->kps[j].octave);
   return 0;
 }
 
-// Copies a host keyframe's arrays into the staging buffer at *off; returns its device twin.
-inline slamgpu_kf stage_kf(const slamgpu_kf& k, bool fv, size_t* off) {
-  char* base = t_stage.buf;
+// Copies a host keyframe's arrays to their places; returns its device twin (arrays without a
+// place are NULL there).
+inline slamgpu_kf upload_kf(const StageLease& S, const slamgpu_kf& k, const KfPlace& p) {
   slamgpu_kf d = k;
-  auto put = [&](const void* src, size_t bytes) -> void* {
-    void* dst = base + *off;
-    *off += al256(bytes ? bytes : 1);
-    if (bytes) (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, t_stage.stream);
+  auto put = [&](size_t at, const void* src, size_t bytes) -> const void* {
+    if (at == kNoSlot) return nullptr;
+    void* dst = S.at<char>(at);
+    if (bytes) (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, S.stream());
     return dst;
   };
-  d.kps = (const slamgpu_keypoint*)put(k.kps, (size_t)k.n * sizeof(slamgpu_keypoint));
-  d.desc = (const uint8_t*)put(k.desc, (size_t)k.n * 32);
-  d.u_right = (const float*)put(k.u_right, (size_t)k.n * 4);
-  d.has_mp = fv ? (const uint8_t*)put(k.has_mp, (size_t)k.n) : nullptr;
-  if (fv && k.n_nodes > 0) {
-    d.nodes = (const uint32_t*)put(k.nodes, (size_t)k.n_nodes * 4);
-    d.node_start = (const int32_t*)put(k.node_start, (size_t)(k.n_nodes + 1) * 4);
-    d.node_feats = (const uint32_t*)put(k.node_feats, (size_t)k.node_start[k.n_nodes] * 4);
-  } else {
-    d.nodes = nullptr;
-    d.node_start = nullptr;
-    d.node_feats = nullptr;
-    d.n_nodes = 0;
-  }
+  d.kps = (const slamgpu_keypoint*)put(p.kps, k.kps, (size_t)k.n * sizeof(slamgpu_keypoint));
+  d.desc = (const uint8_t*)put(p.desc, k.desc, (size_t)k.n * 32);
+  d.u_right = (const float*)put(p.u_right, k.u_right, (size_t)k.n * 4);
+  d.has_mp = (const uint8_t*)put(p.has_mp, k.has_mp, (size_t)k.n);
+  const bool fv = p.nodes != kNoSlot;
+  if (!fv) d.n_nodes = 0;
+  d.nodes = (const uint32_t*)put(p.nodes, k.nodes, (size_t)d.n_nodes * 4);
+  d.node_start = (const int32_t*)put(p.node_start, k.node_start, (size_t)(d.n_nodes + 1) * 4);
+  d.node_feats = (const uint32_t*)put(p.node_feats, k.node_feats,
+                                      fv ? (size_t)k.node_start[k.n_nodes] * 4 : 0);
   return d;
-}
-
-inline size_t kf_bytes(const slamgpu_kf& k, bool fv) {
-  size_t b = al256((size_t)k.n * sizeof(slamgpu_keypoint) + 1) + al256((size_t)k.n * 32 + 1) +
-             al256((size_t)k.n * 4 + 1) + al256((size_t)k.n + 1);
-  if (fv && k.n_nodes > 0)
-    b += al256((size_t)k.n_nodes * 4) + al256((size_t)(k.n_nodes + 1) * 4) +
-         al256((size_t)k.node_start[k.n_nodes] * 4 + 1);
-  return b;
 }
 
 }  // namespace slamgpu

@@ -447,56 +447,22 @@ __global__ __launch_bounds__(256) void sim3_mutual_kernel(
 
 int check_common(const slamgpu_camera* cam, const slamgpu_levels* lv,
                  const slamgpu_kf_grid* grid) {
-  if (!cam || !grid) return fail(SLAMGPU_EINVAL, "NULL camera or grid");
+  if (!cam || !grid) return t_kf_err.fail(SLAMGPU_EINVAL, "NULL camera or grid");
   if (int r = check_levels(lv)) return r;
-  if (!(grid->cell_w > 0) || !(grid->cell_h > 0)) return fail(SLAMGPU_EINVAL, "grid cell size");
-  return 0;
+  return check_grid(grid);
 }
 
 // The Sim3 matchers never read u_right; has_mp and the FeatureVector neither.
 int check_kf_loop(const slamgpu_kf* k, const slamgpu_levels* lv, const char* name) {
-  if (!k) return fail(SLAMGPU_EINVAL, "%s is NULL", name);
+  if (!k) return t_kf_err.fail(SLAMGPU_EINVAL, "%s is NULL", name);
   if (k->n < 0 || k->n > kMaxFeat)
-    return fail(SLAMGPU_EINVAL, "%s: n %d outside [0, %d]", name, k->n, kMaxFeat);
-  if (k->n > 0 && (!k->kps || !k->desc)) return fail(SLAMGPU_EINVAL, "%s: NULL keypoint arrays", name);
+    return t_kf_err.fail(SLAMGPU_EINVAL, "%s: n %d outside [0, %d]", name, k->n, kMaxFeat);
+  if (k->n > 0 && (!k->kps || !k->desc)) return t_kf_err.fail(SLAMGPU_EINVAL, "%s: NULL keypoint arrays", name);
   for (int j = 0; j < k->n; j++)
     if (k->kps[j].octave < 0 || k->kps[j].octave >= lv->nlevels)
-      return fail(SLAMGPU_EINVAL, "%s: keypoint %d octave %d outside [0, nlevels)", name, j,
+      return t_kf_err.fail(SLAMGPU_EINVAL, "%s: keypoint %d octave %d outside [0, nlevels)", name, j,
                   k->kps[j].octave);
   return 0;
-}
-
-size_t kf_loop_bytes(const slamgpu_kf& k) {
-  return al256((size_t)k.n * sizeof(slamgpu_keypoint) + 1) + al256((size_t)k.n * 32 + 1);
-}
-
-slamgpu_kf stage_kf_loop(const slamgpu_kf& k, size_t* off) {
-  char* base = t_stage.buf;
-  slamgpu_kf d = k;
-  auto put = [&](const void* src, size_t bytes) -> void* {
-    void* dst = base + *off;
-    *off += al256(bytes + 1);
-    if (bytes) (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, t_stage.stream);
-    return dst;
-  };
-  d.kps = (const slamgpu_keypoint*)put(k.kps, (size_t)k.n * sizeof(slamgpu_keypoint));
-  d.desc = (const uint8_t*)put(k.desc, (size_t)k.n * 32);
-  d.u_right = nullptr;
-  d.has_mp = nullptr;
-  d.nodes = nullptr;
-  d.node_start = nullptr;
-  d.node_feats = nullptr;
-  d.n_nodes = 0;
-  return d;
-}
-
-// Carves `bytes` out of the staging buffer; uploads src when non-NULL.
-template <typename T>
-T* carve(size_t* off, size_t bytes, const void* src = nullptr) {
-  T* p = reinterpret_cast<T*>(t_stage.buf + *off);
-  *off += al256(bytes + 1);
-  if (src && bytes) (void)hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, t_stage.stream);
-  return p;
 }
 
 }  // namespace
@@ -506,22 +472,22 @@ using namespace slamgpu;
 
 extern "C" {
 
-const char* slamgpu_loopmatch_last_error(void) { return t_err.c_str(); }
+const char* slamgpu_loopmatch_last_error(void) { return t_kf_err.c_str(); }
 
 int slamgpu_fuse_sim3_device(const slamgpu_kf* d_kfs, int n_kfs, const slamgpu_fuse_point* d_pts,
                              int n_pts, const uint8_t* d_skip, float th,
                              const slamgpu_camera* cam, const slamgpu_levels* lv,
                              const slamgpu_kf_grid* grid, int32_t* d_best_idx,
                              int32_t* d_best_dist, void* stream) {
-  if (n_kfs < 0 || n_pts < 0) return fail(SLAMGPU_EINVAL, "n_kfs %d or n_pts %d < 0", n_kfs, n_pts);
+  if (n_kfs < 0 || n_pts < 0) return t_kf_err.fail(SLAMGPU_EINVAL, "n_kfs %d or n_pts %d < 0", n_kfs, n_pts);
   if (n_kfs == 0 || n_pts == 0) return 0;
-  if (n_kfs > 65535) return fail(SLAMGPU_EINVAL, "n_kfs %d > 65535", n_kfs);
-  if (!d_kfs || !d_pts || !d_best_idx || !d_best_dist) return fail(SLAMGPU_EINVAL, "NULL argument");
+  if (n_kfs > 65535) return t_kf_err.fail(SLAMGPU_EINVAL, "n_kfs %d > 65535", n_kfs);
+  if (!d_kfs || !d_pts || !d_best_idx || !d_best_dist) return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
   if (int r = check_common(cam, lv, grid)) return r;
   hipLaunchKernelGGL(fuse_sim3_kernel, dim3((n_pts + kChunk - 1) / kChunk, n_kfs),
                      dim3(64 * kScanWaves), 0, static_cast<hipStream_t>(stream), d_kfs, d_pts,
                      d_skip, n_pts, th, *cam, *lv, *grid, d_best_idx, d_best_dist);
-  KF_HIPCHECK(hipGetLastError());
+  HIPCHECK(t_kf_err, hipGetLastError());
   return 0;
 }
 
@@ -531,28 +497,27 @@ int slamgpu_fuse_sim3(const slamgpu_kf* kf, const slamgpu_fuse_point* pts, int n
                       int* nfused) {
   if (int r = check_common(cam, lv, grid)) return r;
   if (int r = check_kf_loop(kf, lv, "kf")) return r;
-  if (n_pts < 0) return fail(SLAMGPU_EINVAL, "n_pts %d < 0", n_pts);
+  if (n_pts < 0) return t_kf_err.fail(SLAMGPU_EINVAL, "n_pts %d < 0", n_pts);
   if (!nfused || (n_pts > 0 && (!pts || !best_idx || !best_dist)))
-    return fail(SLAMGPU_EINVAL, "NULL argument");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
   *nfused = 0;
   if (n_pts == 0) return 0;
   const size_t pbytes = (size_t)n_pts * sizeof(slamgpu_fuse_point), obytes = (size_t)n_pts * 4;
-  if (int r = stage_reserve(kf_loop_bytes(*kf) + al256(sizeof(slamgpu_kf) + 1) +
-                            al256(pbytes + 1) + 2 * al256(obytes + 1)))
+  StageLease S(t_kf_err);
+  StageLayout L;
+  const FuseLayout f = layout_fuse(L, kKfLoop, kf->n, n_pts);
+  if (int r = S.reserve(L.size())) return r;
+  hipStream_t st = S.stream();
+  const slamgpu_kf dk = upload_kf(S, *kf, f.kf);
+  HIPCHECK(t_kf_err, S.upload(f.kfs, &dk, sizeof(dk)));
+  HIPCHECK(t_kf_err, S.upload(f.pts, pts, pbytes));
+  if (int r = slamgpu_fuse_sim3_device(S.at<slamgpu_kf>(f.kfs), 1, S.at<slamgpu_fuse_point>(f.pts),
+                                       n_pts, nullptr, th, cam, lv, grid, S.at<int32_t>(f.best_idx),
+                                       S.at<int32_t>(f.best_dist), st))
     return r;
-  size_t off = 0;
-  const slamgpu_kf dk = stage_kf_loop(*kf, &off);
-  hipStream_t st = t_stage.stream;
-  slamgpu_kf* d_kf = carve<slamgpu_kf>(&off, sizeof(dk), &dk);
-  slamgpu_fuse_point* d_pts = carve<slamgpu_fuse_point>(&off, pbytes, pts);
-  int32_t* d_idx = carve<int32_t>(&off, obytes);
-  int32_t* d_dist = carve<int32_t>(&off, obytes);
-  if (int r = slamgpu_fuse_sim3_device(d_kf, 1, d_pts, n_pts, nullptr, th, cam, lv, grid, d_idx,
-                                       d_dist, st))
-    return r;
-  KF_HIPCHECK(hipMemcpyAsync(best_idx, d_idx, obytes, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipMemcpyAsync(best_dist, d_dist, obytes, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipStreamSynchronize(st));
+  HIPCHECK(t_kf_err, S.download(best_idx, f.best_idx, obytes));
+  HIPCHECK(t_kf_err, S.download(best_dist, f.best_dist, obytes));
+  HIPCHECK(t_kf_err, hipStreamSynchronize(st));
   int nf = 0;
   for (int i = 0; i < n_pts; i++) nf += best_idx[i] >= 0;
   *nfused = nf;
@@ -570,14 +535,14 @@ int slamgpu_search_by_projection_sim3_device(
     const slamgpu_kf_grid* grid, int32_t* d_kp_point, int32_t* d_point_kp, int32_t* d_nmatches,
     void* d_scratch, size_t scratch_bytes, void* stream) {
   if (n_jobs < 0 || n_pts_total < 0 || n_kp_total < 0 || max_job_pts < 0)
-    return fail(SLAMGPU_EINVAL, "negative count");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "negative count");
   if (n_jobs == 0) return 0;
-  if (n_jobs > 65535) return fail(SLAMGPU_EINVAL, "n_jobs %d > 65535", n_jobs);
+  if (n_jobs > 65535) return t_kf_err.fail(SLAMGPU_EINVAL, "n_jobs %d > 65535", n_jobs);
   if (!d_kfs || !d_jobs || !d_nmatches || (n_pts_total > 0 && (!d_pts || !d_point_kp || !d_scratch)) ||
       (n_kp_total > 0 && (!d_matched_in || !d_kp_point)))
-    return fail(SLAMGPU_EINVAL, "NULL argument");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
   if (scratch_bytes < slamgpu_search_by_projection_sim3_scratch_bytes(n_pts_total))
-    return fail(SLAMGPU_EINVAL, "scratch_bytes %zu < %zu", scratch_bytes,
+    return t_kf_err.fail(SLAMGPU_EINVAL, "scratch_bytes %zu < %zu", scratch_bytes,
                 slamgpu_search_by_projection_sim3_scratch_bytes(n_pts_total));
   if (int r = check_common(cam, lv, grid)) return r;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -589,7 +554,7 @@ int slamgpu_search_by_projection_sim3_device(
   hipLaunchKernelGGL(sbp_resolve_kernel, dim3(n_jobs), dim3(64), 0, st, d_kfs, d_pts, n_pts_total,
                      d_jobs, max_job_pts, d_matched_in, n_kp_total, th, *cam, *lv, *grid,
                      static_cast<const int32_t*>(d_scratch), d_kp_point, d_point_kp, d_nmatches);
-  KF_HIPCHECK(hipGetLastError());
+  HIPCHECK(t_kf_err, hipGetLastError());
   return 0;
 }
 
@@ -600,9 +565,9 @@ int slamgpu_search_by_projection_sim3(const slamgpu_kf* kf, const slamgpu_fuse_p
                                       int32_t* point_kp, int* nmatches) {
   if (int r = check_common(cam, lv, grid)) return r;
   if (int r = check_kf_loop(kf, lv, "kf")) return r;
-  if (n_pts < 0) return fail(SLAMGPU_EINVAL, "n_pts %d < 0", n_pts);
+  if (n_pts < 0) return t_kf_err.fail(SLAMGPU_EINVAL, "n_pts %d < 0", n_pts);
   if (!nmatches || (n_pts > 0 && (!pts || !point_kp)) || (kf->n > 0 && (!matched_in || !kp_point)))
-    return fail(SLAMGPU_EINVAL, "NULL argument");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
   *nmatches = 0;
   if (n_pts == 0 || kf->n == 0) {
     for (int i = 0; i < n_pts; i++) point_kp[i] = -1;
@@ -612,33 +577,29 @@ int slamgpu_search_by_projection_sim3(const slamgpu_kf* kf, const slamgpu_fuse_p
   const int n = kf->n;
   const size_t pbytes = (size_t)n_pts * sizeof(slamgpu_fuse_point);
   const size_t sbytes = slamgpu_search_by_projection_sim3_scratch_bytes(n_pts);
-  if (int r = stage_reserve(kf_loop_bytes(*kf) + al256(sizeof(slamgpu_kf) + 1) + al256(pbytes + 1) +
-                            al256(sizeof(slamgpu_sbp_job) + 1) + al256((size_t)n + 1) +
-                            al256((size_t)n * 4 + 1) + al256((size_t)n_pts * 4 + 1) + al256(5) +
-                            al256(sbytes + 1)))
-    return r;
-  size_t off = 0;
-  const slamgpu_kf dk = stage_kf_loop(*kf, &off);
-  hipStream_t st = t_stage.stream;
+  StageLease S(t_kf_err);
+  StageLayout L;
+  const SbpSim3Layout l = layout_sbp_sim3(L, n, n_pts, sbytes);
+  if (int r = S.reserve(L.size())) return r;
+  hipStream_t st = S.stream();
+  const slamgpu_kf dk = upload_kf(S, *kf, l.kf);
   const slamgpu_sbp_job job{0, 0, n_pts, 0};
-  slamgpu_kf* d_kf = carve<slamgpu_kf>(&off, sizeof(dk), &dk);
-  slamgpu_fuse_point* d_pts = carve<slamgpu_fuse_point>(&off, pbytes, pts);
-  slamgpu_sbp_job* d_job = carve<slamgpu_sbp_job>(&off, sizeof(job), &job);
-  uint8_t* d_min = carve<uint8_t>(&off, (size_t)n, matched_in);
-  int32_t* d_kpp = carve<int32_t>(&off, (size_t)n * 4);
-  int32_t* d_pkp = carve<int32_t>(&off, (size_t)n_pts * 4);
-  int32_t* d_nm = carve<int32_t>(&off, 4);
-  void* d_scr = carve<char>(&off, sbytes);
-  if (int r = slamgpu_search_by_projection_sim3_device(d_kf, d_pts, n_pts, d_job, 1, n_pts, d_min,
-                                                       n, th, cam, lv, grid, d_kpp, d_pkp, d_nm,
-                                                       d_scr, sbytes, st))
+  HIPCHECK(t_kf_err, S.upload(l.kfs, &dk, sizeof(dk)));
+  HIPCHECK(t_kf_err, S.upload(l.pts, pts, pbytes));
+  HIPCHECK(t_kf_err, S.upload(l.job, &job, sizeof(job)));
+  HIPCHECK(t_kf_err, S.upload(l.matched_in, matched_in, (size_t)n));
+  if (int r = slamgpu_search_by_projection_sim3_device(
+          S.at<slamgpu_kf>(l.kfs), S.at<slamgpu_fuse_point>(l.pts), n_pts,
+          S.at<slamgpu_sbp_job>(l.job), 1, n_pts, S.at<uint8_t>(l.matched_in), n, th, cam, lv, grid,
+          S.at<int32_t>(l.kp_point), S.at<int32_t>(l.point_kp), S.at<int32_t>(l.nmatches),
+          S.at<char>(l.scratch), sbytes, st))
     return r;
   int32_t nm = 0;
-  KF_HIPCHECK(hipMemcpyAsync(kp_point, d_kpp, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipMemcpyAsync(point_kp, d_pkp, (size_t)n_pts * 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipMemcpyAsync(&nm, d_nm, 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipStreamSynchronize(st));
-  if (nm < 0) return fail(SLAMGPU_EINVAL, "job rejected on the device");
+  HIPCHECK(t_kf_err, S.download(kp_point, l.kp_point, (size_t)n * 4));
+  HIPCHECK(t_kf_err, S.download(point_kp, l.point_kp, (size_t)n_pts * 4));
+  HIPCHECK(t_kf_err, S.download(&nm, l.nmatches, 4));
+  HIPCHECK(t_kf_err, hipStreamSynchronize(st));
+  if (nm < 0) return t_kf_err.fail(SLAMGPU_EINVAL, "job rejected on the device");
   *nmatches = nm;
   return 0;
 }
@@ -650,13 +611,13 @@ int slamgpu_search_by_sim3_device(const slamgpu_kf* d_kfs, const slamgpu_fuse_po
                                   const slamgpu_levels* lv, const slamgpu_kf_grid* grid,
                                   int32_t* d_match12, int32_t* d_vn_match1,
                                   int32_t* d_vn_match2, int32_t* d_nfound, void* stream) {
-  if (n_pairs < 0 || n_mp_total < 0 || stride < 0) return fail(SLAMGPU_EINVAL, "negative count");
+  if (n_pairs < 0 || n_mp_total < 0 || stride < 0) return t_kf_err.fail(SLAMGPU_EINVAL, "negative count");
   if (n_pairs == 0) return 0;
-  if (n_pairs > 65535) return fail(SLAMGPU_EINVAL, "n_pairs %d > 65535", n_pairs);
+  if (n_pairs > 65535) return t_kf_err.fail(SLAMGPU_EINVAL, "n_pairs %d > 65535", n_pairs);
   if (!d_kfs || !d_pairs || !d_nfound ||
       (stride > 0 && (!d_mp || !d_already1 || !d_already2 || !d_match12 || !d_vn_match1 ||
                       !d_vn_match2)))
-    return fail(SLAMGPU_EINVAL, "NULL argument");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
   if (int r = check_common(cam, lv, grid)) return r;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t cap = stride < kMaxFeat ? stride : kMaxFeat;
@@ -666,7 +627,7 @@ int slamgpu_search_by_sim3_device(const slamgpu_kf* d_kfs, const slamgpu_fuse_po
                        d_already2, stride, th, *cam, *lv, *grid, d_vn_match1, d_vn_match2);
   hipLaunchKernelGGL(sim3_mutual_kernel, dim3(n_pairs), dim3(256), 0, st, d_kfs, d_pairs,
                      n_mp_total, stride, d_vn_match1, d_vn_match2, d_match12, d_nfound);
-  KF_HIPCHECK(hipGetLastError());
+  HIPCHECK(t_kf_err, hipGetLastError());
   return 0;
 }
 
@@ -684,7 +645,7 @@ int slamgpu_search_by_sim3(const slamgpu_kf* kf1, const slamgpu_kf* kf2,
   if (!nfound || !sR12 || !t12 || !sR21 || !t21 ||
       (n1 > 0 && (!mp1 || !already1 || !match12 || !vn_match1)) ||
       (n2 > 0 && (!mp2 || !already2 || !vn_match2)))
-    return fail(SLAMGPU_EINVAL, "NULL argument");
+    return t_kf_err.fail(SLAMGPU_EINVAL, "NULL argument");
   *nfound = 0;
   if (n1 == 0 || n2 == 0) {
     for (int i = 0; i < n1; i++) match12[i] = vn_match1[i] = -1;
@@ -692,15 +653,12 @@ int slamgpu_search_by_sim3(const slamgpu_kf* kf1, const slamgpu_kf* kf2,
     return 0;
   }
   const int stride = n1 > n2 ? n1 : n2;
-  const size_t mbytes = (size_t)(n1 + n2) * sizeof(slamgpu_fuse_point);
-  if (int r = stage_reserve(kf_loop_bytes(*kf1) + kf_loop_bytes(*kf2) +
-                            al256(2 * sizeof(slamgpu_kf) + 1) + al256(mbytes + 1) +
-                            al256(sizeof(slamgpu_sim3_pair) + 1) + 2 * al256((size_t)stride + 1) +
-                            3 * al256((size_t)stride * 4 + 1) + al256(5)))
-    return r;
-  size_t off = 0;
-  const slamgpu_kf dk[2] = {stage_kf_loop(*kf1, &off), stage_kf_loop(*kf2, &off)};
-  hipStream_t st = t_stage.stream;
+  StageLease S(t_kf_err);
+  StageLayout L;
+  const SearchSim3Layout l = layout_search_sim3(L, n1, n2);
+  if (int r = S.reserve(L.size())) return r;
+  hipStream_t st = S.stream();
+  const slamgpu_kf dk[2] = {upload_kf(S, *kf1, l.kf[0]), upload_kf(S, *kf2, l.kf[1])};
   slamgpu_sim3_pair pr{};
   pr.kf1 = 0;
   pr.kf2 = 1;
@@ -714,31 +672,26 @@ int slamgpu_search_by_sim3(const slamgpu_kf* kf1, const slamgpu_kf* kf2,
     pr.t12[i] = t12[i];
     pr.t21[i] = t21[i];
   }
-  slamgpu_kf* d_kfs = carve<slamgpu_kf>(&off, sizeof(dk), dk);
-  slamgpu_fuse_point* d_mp = carve<slamgpu_fuse_point>(&off, mbytes);
-  KF_HIPCHECK(hipMemcpyAsync(d_mp, mp1, (size_t)n1 * sizeof(slamgpu_fuse_point),
-                             hipMemcpyHostToDevice, st));
-  KF_HIPCHECK(hipMemcpyAsync(d_mp + n1, mp2, (size_t)n2 * sizeof(slamgpu_fuse_point),
-                             hipMemcpyHostToDevice, st));
-  slamgpu_sim3_pair* d_pair = carve<slamgpu_sim3_pair>(&off, sizeof(pr), &pr);
-  uint8_t* d_a1 = carve<uint8_t>(&off, (size_t)stride);
-  uint8_t* d_a2 = carve<uint8_t>(&off, (size_t)stride);
-  KF_HIPCHECK(hipMemcpyAsync(d_a1, already1, (size_t)n1, hipMemcpyHostToDevice, st));
-  KF_HIPCHECK(hipMemcpyAsync(d_a2, already2, (size_t)n2, hipMemcpyHostToDevice, st));
-  int32_t* d_m12 = carve<int32_t>(&off, (size_t)stride * 4);
-  int32_t* d_v1 = carve<int32_t>(&off, (size_t)stride * 4);
-  int32_t* d_v2 = carve<int32_t>(&off, (size_t)stride * 4);
-  int32_t* d_nf = carve<int32_t>(&off, 4);
-  if (int r = slamgpu_search_by_sim3_device(d_kfs, d_mp, n1 + n2, d_pair, 1, d_a1, d_a2, stride, th,
-                                            cam, lv, grid, d_m12, d_v1, d_v2, d_nf, st))
+  const size_t pt = sizeof(slamgpu_fuse_point);
+  HIPCHECK(t_kf_err, S.upload(l.kfs, dk, sizeof(dk)));
+  HIPCHECK(t_kf_err, S.upload(l.mp, mp1, (size_t)n1 * pt));
+  HIPCHECK(t_kf_err, S.upload(l.mp + (size_t)n1 * pt, mp2, (size_t)n2 * pt));
+  HIPCHECK(t_kf_err, S.upload(l.pair, &pr, sizeof(pr)));
+  HIPCHECK(t_kf_err, S.upload(l.already1, already1, (size_t)n1));
+  HIPCHECK(t_kf_err, S.upload(l.already2, already2, (size_t)n2));
+  if (int r = slamgpu_search_by_sim3_device(
+          S.at<slamgpu_kf>(l.kfs), S.at<slamgpu_fuse_point>(l.mp), n1 + n2,
+          S.at<slamgpu_sim3_pair>(l.pair), 1, S.at<uint8_t>(l.already1), S.at<uint8_t>(l.already2),
+          stride, th, cam, lv, grid, S.at<int32_t>(l.match12), S.at<int32_t>(l.vn_match1),
+          S.at<int32_t>(l.vn_match2), S.at<int32_t>(l.nfound), st))
     return r;
   int32_t nf = 0;
-  KF_HIPCHECK(hipMemcpyAsync(match12, d_m12, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipMemcpyAsync(vn_match1, d_v1, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipMemcpyAsync(vn_match2, d_v2, (size_t)n2 * 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipMemcpyAsync(&nf, d_nf, 4, hipMemcpyDeviceToHost, st));
-  KF_HIPCHECK(hipStreamSynchronize(st));
-  if (nf < 0) return fail(SLAMGPU_EINVAL, "pair rejected on the device");
+  HIPCHECK(t_kf_err, S.download(match12, l.match12, (size_t)n1 * 4));
+  HIPCHECK(t_kf_err, S.download(vn_match1, l.vn_match1, (size_t)n1 * 4));
+  HIPCHECK(t_kf_err, S.download(vn_match2, l.vn_match2, (size_t)n2 * 4));
+  HIPCHECK(t_kf_err, S.download(&nf, l.nfound, 4));
+  HIPCHECK(t_kf_err, hipStreamSynchronize(st));
+  if (nf < 0) return t_kf_err.fail(SLAMGPU_EINVAL, "pair rejected on the device");
   *nfound = nf;
   return 0;
 }

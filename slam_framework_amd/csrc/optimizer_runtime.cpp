@@ -2,8 +2,8 @@
 //
 // The device call validates its scalar arguments and launches one kernel on the caller's
 // stream. The host call (the per-frame drop-in for Optimizer::PoseOptimization) stages the
-// frame's edges through a per-thread device buffer that grows on demand, runs the same kernel
-// on a per-thread stream and synchronises.
+// frame's edges through the calling thread's buffer (host_stage.h), runs the same kernel on that
+// thread's stream and synchronises.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -12,7 +12,6 @@
 #include <thread>
 
 #include <cfloat>
-#include <cstdarg>
 #include <cstdio>
 #include <algorithm>
 #include <cmath>
@@ -25,35 +24,19 @@
 #include "ba_coop.h"
 #include "ba_kernels.h"
 #include "eg_kernels.h"
+#include "host_stage.h"
 #include "pose_kernels.h"
 #include "sim3_kernels.h"
+#include "stage_layout.h"
 
 using namespace slamgpu;
 
 namespace {
 
-thread_local std::string t_err;
-
-int fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  t_err = buf;
-  return code;
-}
-
-#define OPT_HIPCHECK(x)                                                                 \
-  do {                                                                                  \
-    hipError_t e_ = (x);                                                                \
-    if (e_ != hipSuccess) return fail(SLAMGPU_EHIP, "%s failed: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
 int make_params(const slamgpu_camera* cam, const float* inv_sigma2, int nlevels, PoseParams* P) {
-  if (!cam || !inv_sigma2) return fail(SLAMGPU_EINVAL, "camera and inv_sigma2 are required");
+  if (!cam || !inv_sigma2) return t_opt_err.fail(SLAMGPU_EINVAL, "camera and inv_sigma2 are required");
   if (nlevels < 1 || nlevels > SLAMGPU_MAX_LEVELS)
-    return fail(SLAMGPU_EINVAL, "nlevels %d outside [1, %d]", nlevels, SLAMGPU_MAX_LEVELS);
+    return t_opt_err.fail(SLAMGPU_EINVAL, "nlevels %d outside [1, %d]", nlevels, SLAMGPU_MAX_LEVELS);
   std::memset(P, 0, sizeof(*P));
   P->fx = cam->fx;
   P->fy = cam->fy;
@@ -65,61 +48,34 @@ int make_params(const slamgpu_camera* cam, const float* inv_sigma2, int nlevels,
   return 0;
 }
 
-// Per-thread staging buffer of the synchronous calls (grown on demand).
-struct HostStage {
+// What the single-problem BA calls keep per calling thread beside the shared stage: dropped when
+// the stage moves to another device, otherwise never freed (as the stage itself).
+struct CoopExtras {
   int device = -1;
-  hipStream_t stream = nullptr;
-  void* buf = nullptr;
-  size_t bytes = 0;
   // host-mapped mirror of a caller's stop flag, polled by the local BA kernel
   int32_t* stop_host = nullptr;
   int32_t* stop_dev = nullptr;
-  // pinned host twin of the inputs / outputs region of the single-problem BA calls
+  // pinned host twin of the inputs / outputs region
   char* pin = nullptr;
   size_t pin_bytes = 0;
 };
-// One per calling thread, never destroyed: its device / pinned buffers and stream live until the
-// process ends (the runtime reclaims them); freeing them from a thread-exit destructor at process
-// exit would run after the HIP runtime's own teardown has begun.
-HostStage& thread_stage() {
-  thread_local HostStage* s = new HostStage();
-  return *s;
-}
-
-int stage_reserve(HostStage& S, size_t need) {
-  int dev = 0;
-  OPT_HIPCHECK(hipGetDevice(&dev));
-  if (S.device != dev) {
-    if (S.buf) (void)hipFree(S.buf);
-    if (S.stop_host) (void)hipHostFree(S.stop_host);
-    if (S.stream) (void)hipStreamDestroy(S.stream);
-    S.buf = nullptr;
-    S.stop_host = S.stop_dev = nullptr;
-    S.stream = nullptr;
-    S.bytes = 0;
-    OPT_HIPCHECK(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
-    S.device = dev;
+CoopExtras& coop_extras(int device) {
+  thread_local CoopExtras* x = new CoopExtras();
+  if (x->device != device) {
+    if (x->stop_host) (void)hipHostFree(x->stop_host);
+    x->stop_host = x->stop_dev = nullptr;
+    x->device = device;
   }
-  if (need > S.bytes) {
-    if (S.buf) OPT_HIPCHECK(hipFree(S.buf));
-    S.buf = nullptr;
-    S.bytes = 0;
-    const size_t cap = need < (1u << 20) ? (1u << 20) : need;
-    OPT_HIPCHECK(hipMalloc(&S.buf, cap));
-    S.bytes = cap;
-  }
-  return 0;
+  return *x;
 }
-
-size_t al256(size_t x) { return (x + 255) / 256 * 256; }
 
 int make_sim3_params(const float K1[4], const float K2[4], const float* isig1, const float* isig2,
                      int nlevels, float th2, int fix_scale, Sim3Params* P) {
   if (!K1 || !K2 || !isig1 || !isig2)
-    return fail(SLAMGPU_EINVAL, "calibrations and inv_sigma2 arrays are required");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "calibrations and inv_sigma2 arrays are required");
   if (nlevels < 1 || nlevels > SLAMGPU_MAX_LEVELS)
-    return fail(SLAMGPU_EINVAL, "nlevels %d outside [1, %d]", nlevels, SLAMGPU_MAX_LEVELS);
-  if (!(th2 >= 0.f)) return fail(SLAMGPU_EINVAL, "th2 %g is not a threshold", (double)th2);
+    return t_opt_err.fail(SLAMGPU_EINVAL, "nlevels %d outside [1, %d]", nlevels, SLAMGPU_MAX_LEVELS);
+  if (!(th2 >= 0.f)) return t_opt_err.fail(SLAMGPU_EINVAL, "th2 %g is not a threshold", (double)th2);
   std::memset(P, 0, sizeof(*P));
   for (int i = 0; i < 4; i++) {
     P->K1[i] = (double)K1[i];
@@ -140,7 +96,7 @@ int make_sim3_params(const float K1[4], const float K2[4], const float* isig1, c
 
 extern "C" {
 
-const char* slamgpu_optimizer_last_error(void) { return t_err.c_str(); }
+const char* slamgpu_optimizer_last_error(void) { return t_opt_err.c_str(); }
 
 int slamgpu_pose_optimization_device(const slamgpu_camera* cam, const float* inv_sigma2,
                                      int nlevels, const slamgpu_pose_edge* d_edges,
@@ -149,10 +105,10 @@ int slamgpu_pose_optimization_device(const slamgpu_camera* cam, const float* inv
                                      int32_t* d_lm_iterations, void* stream) {
   PoseParams P;
   if (int r = make_params(cam, inv_sigma2, nlevels, &P)) return r;
-  if (n_frames < 0) return fail(SLAMGPU_EINVAL, "n_frames %d < 0", n_frames);
+  if (n_frames < 0) return t_opt_err.fail(SLAMGPU_EINVAL, "n_frames %d < 0", n_frames);
   if (n_frames > 0 && (!d_edge_start || !d_Tcw || !d_n_inliers || !d_edges || !d_outlier))
-    return fail(SLAMGPU_EINVAL, "null device buffer");
-  OPT_HIPCHECK(launch_pose_optimization(d_edges, d_edge_start, n_frames, P, d_Tcw, d_outlier,
+    return t_opt_err.fail(SLAMGPU_EINVAL, "null device buffer");
+  HIPCHECK(t_opt_err, launch_pose_optimization(d_edges, d_edge_start, n_frames, P, d_Tcw, d_outlier,
                                         d_n_inliers, d_lm_iterations,
                                         static_cast<hipStream_t>(stream)));
   return 0;
@@ -164,33 +120,28 @@ int slamgpu_pose_optimization(const slamgpu_camera* cam, const float* inv_sigma2
   PoseParams P;
   if (int r = make_params(cam, inv_sigma2, nlevels, &P)) return r;
   if (!Tcw || !n_inliers || n < 0 || (n > 0 && (!edges || !outlier)))
-    return fail(SLAMGPU_EINVAL, "bad arguments");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "bad arguments");
   if (n > SLAMGPU_POSE_MAX_EDGES)
-    return fail(SLAMGPU_ECAP, "%d edges > SLAMGPU_POSE_MAX_EDGES (%d)", n, SLAMGPU_POSE_MAX_EDGES);
+    return t_opt_err.fail(SLAMGPU_ECAP, "%d edges > SLAMGPU_POSE_MAX_EDGES (%d)", n, SLAMGPU_POSE_MAX_EDGES);
   for (int i = 0; i < n; i++)
     if (edges[i].octave < 0 || edges[i].octave >= nlevels)
-      return fail(SLAMGPU_EINVAL, "edge %d: octave %d outside [0, %d)", i, edges[i].octave, nlevels);
-  HostStage& S = thread_stage();
-  const size_t off_e = 256, off_T = off_e + al256((size_t)n * sizeof(slamgpu_pose_edge));
-  const size_t off_o = off_T + 256, off_r = off_o + al256((size_t)n);
-  if (int r = stage_reserve(S, off_r + 256)) return r;
-  char* b = static_cast<char*>(S.buf);
+      return t_opt_err.fail(SLAMGPU_EINVAL, "edge %d: octave %d outside [0, %d)", i, edges[i].octave, nlevels);
+  StageLease S(t_opt_err);
+  StageLayout L;
+  const SolveLayout l = layout_solve(L, n, sizeof(slamgpu_pose_edge), 16 * sizeof(float));
+  if (int r = S.reserve(L.size())) return r;
   const int32_t start[2] = {0, n};
-  OPT_HIPCHECK(hipMemcpyAsync(b, start, sizeof(start), hipMemcpyHostToDevice, S.stream));
-  if (n > 0)
-    OPT_HIPCHECK(hipMemcpyAsync(b + off_e, edges, (size_t)n * sizeof(slamgpu_pose_edge),
-                                hipMemcpyHostToDevice, S.stream));
-  OPT_HIPCHECK(hipMemcpyAsync(b + off_T, Tcw, 16 * sizeof(float), hipMemcpyHostToDevice, S.stream));
-  OPT_HIPCHECK(launch_pose_optimization(
-      reinterpret_cast<const slamgpu_pose_edge*>(b + off_e), reinterpret_cast<int32_t*>(b), 1, P,
-      reinterpret_cast<float*>(b + off_T), reinterpret_cast<uint8_t*>(b + off_o),
-      reinterpret_cast<int32_t*>(b + off_r), nullptr, S.stream, n));
+  HIPCHECK(t_opt_err, S.upload(l.start, start, sizeof(start)));
+  HIPCHECK(t_opt_err, S.upload(l.items, edges, (size_t)n * sizeof(slamgpu_pose_edge)));
+  HIPCHECK(t_opt_err, S.upload(l.state, Tcw, 16 * sizeof(float)));
+  HIPCHECK(t_opt_err, launch_pose_optimization(
+      S.at<slamgpu_pose_edge>(l.items), S.at<int32_t>(l.start), 1, P, S.at<float>(l.state),
+      S.at<uint8_t>(l.flags), S.at<int32_t>(l.result), nullptr, S.stream(), n));
   int32_t res = 0;
-  OPT_HIPCHECK(hipMemcpyAsync(&res, b + off_r, sizeof(res), hipMemcpyDeviceToHost, S.stream));
-  OPT_HIPCHECK(hipMemcpyAsync(Tcw, b + off_T, 16 * sizeof(float), hipMemcpyDeviceToHost, S.stream));
-  if (n > 0)
-    OPT_HIPCHECK(hipMemcpyAsync(outlier, b + off_o, n, hipMemcpyDeviceToHost, S.stream));
-  OPT_HIPCHECK(hipStreamSynchronize(S.stream));
+  HIPCHECK(t_opt_err, S.download(&res, l.result, sizeof(res)));
+  HIPCHECK(t_opt_err, S.download(Tcw, l.state, 16 * sizeof(float)));
+  HIPCHECK(t_opt_err, S.download(outlier, l.flags, (size_t)n));
+  HIPCHECK(t_opt_err, hipStreamSynchronize(S.stream()));
   *n_inliers = res;
   return 0;
 }
@@ -212,17 +163,17 @@ int slamgpu_local_bundle_adjustment_device(
   PoseParams P;
   if (int r = make_params(cam, inv_sigma2, nlevels, &P)) return r;
   if (n_problems < 0 || total_kf < 0 || total_points < 0 || total_obs < 0)
-    return fail(SLAMGPU_EINVAL, "negative sizes");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "negative sizes");
   if (n_problems == 0) return 0;
   if (!d_problems || !d_kf_Tcw || !d_kf_mode || !d_point_obs_start || !d_status ||
       (total_points > 0 && !d_points) || (total_obs > 0 && (!d_obs || !d_erase)))
-    return fail(SLAMGPU_EINVAL, "null device buffer");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "null device buffer");
   size_t need = 0;
   ba_workspace_layout(nullptr, total_kf, total_points, total_obs, &need);
   if (!d_workspace || workspace_bytes < need)
-    return fail(SLAMGPU_ECAP, "workspace of %zu bytes < %zu needed", workspace_bytes, need);
+    return t_opt_err.fail(SLAMGPU_ECAP, "workspace of %zu bytes < %zu needed", workspace_bytes, need);
   const BaWorkspace ws = ba_workspace_layout(d_workspace, total_kf, total_points, total_obs, nullptr);
-  OPT_HIPCHECK(launch_local_ba(P, d_problems, n_problems, d_kf_Tcw, d_kf_mode, d_points,
+  HIPCHECK(t_opt_err, launch_local_ba(P, d_problems, n_problems, d_kf_Tcw, d_kf_mode, d_points,
                                d_point_obs_start, d_obs, d_erase, d_status, ws, d_stop_flag,
                                static_cast<hipStream_t>(stream)));
   return 0;
@@ -238,19 +189,19 @@ int slamgpu_local_ba_linearize_device(
   PoseParams P;
   if (int r = make_params(cam, inv_sigma2, nlevels, &P)) return r;
   if (n_problems < 0 || total_kf < 0 || total_points < 0 || total_obs < 0 || !out)
-    return fail(SLAMGPU_EINVAL, "bad arguments");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "bad arguments");
   if (n_problems == 0) return 0;
   if (!d_problems || !d_kf_Tcw || !d_kf_mode || !d_point_obs_start || !d_status || !out->chi ||
       (total_points > 0 && (!d_points || !out->hll || !out->bl)) ||
       (total_obs > 0 && (!d_obs || !out->chi2 || !out->hpl)) || !out->hpp || !out->bp)
-    return fail(SLAMGPU_EINVAL, "null device buffer");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "null device buffer");
   size_t need = 0;
   ba_workspace_layout(nullptr, total_kf, total_points, total_obs, &need);
   if (!d_workspace || workspace_bytes < need)
-    return fail(SLAMGPU_ECAP, "workspace of %zu bytes < %zu needed", workspace_bytes, need);
+    return t_opt_err.fail(SLAMGPU_ECAP, "workspace of %zu bytes < %zu needed", workspace_bytes, need);
   const BaWorkspace ws = ba_workspace_layout(d_workspace, total_kf, total_points, total_obs, nullptr);
   const BaLinearOut o{out->chi2, out->hpl, out->hll, out->bl, out->hpp, out->bp, out->chi};
-  OPT_HIPCHECK(launch_local_ba_linearize(P, d_problems, n_problems, d_kf_Tcw, d_kf_mode, d_points,
+  HIPCHECK(t_opt_err, launch_local_ba_linearize(P, d_problems, n_problems, d_kf_Tcw, d_kf_mode, d_points,
                                          d_point_obs_start, d_obs, d_status, ws, o,
                                          static_cast<hipStream_t>(stream)));
   return 0;
@@ -367,14 +318,14 @@ int coop_host(const char* what, const slamgpu_camera* cam, const float* inv_sigm
   if (int r = make_params(cam, inv_sigma2, nlevels, &P)) return r;
   if (lm_iterations) *lm_iterations = 0;
   if (n_kf < 0 || n_points < 0 || !kf_Tcw || !kf_mode || !point_obs_start || (n_points && !points))
-    return fail(SLAMGPU_EINVAL, "%s: bad arguments", what);
-  if (point_obs_start[0] != 0) return fail(SLAMGPU_EINVAL, "point_obs_start[0] must be 0");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "%s: bad arguments", what);
+  if (point_obs_start[0] != 0) return t_opt_err.fail(SLAMGPU_EINVAL, "point_obs_start[0] must be 0");
   const int n_obs = point_obs_start[n_points];
   if (n_obs < 0 || (n_obs > 0 && !obs) || (local && n_obs > 0 && !erase))
-    return fail(SLAMGPU_EINVAL, "%s: bad observations", what);
+    return t_opt_err.fail(SLAMGPU_EINVAL, "%s: bad observations", what);
   std::vector<int32_t> free_of(n_kf, -1), kf_of;
   for (int k = 0; k < n_kf; k++) {
-    if (kf_mode[k] > SLAMGPU_KF_FIXED) return fail(SLAMGPU_EINVAL, "kf_mode[%d] = %d", k, kf_mode[k]);
+    if (kf_mode[k] > SLAMGPU_KF_FIXED) return t_opt_err.fail(SLAMGPU_EINVAL, "kf_mode[%d] = %d", k, kf_mode[k]);
     if (kf_mode[k] == SLAMGPU_KF_LOCAL) {
       free_of[k] = (int32_t)kf_of.size();
       kf_of.push_back(k);
@@ -382,27 +333,27 @@ int coop_host(const char* what, const slamgpu_camera* cam, const float* inv_sigm
   }
   const int K = (int)kf_of.size();
   if (K > SLAMGPU_BA_COOP_MAX_KF)
-    return fail(SLAMGPU_ECAP, "%s: %d optimised keyframes > SLAMGPU_BA_COOP_MAX_KF (%d)", what, K,
+    return t_opt_err.fail(SLAMGPU_ECAP, "%s: %d optimised keyframes > SLAMGPU_BA_COOP_MAX_KF (%d)", what, K,
                 SLAMGPU_BA_COOP_MAX_KF);
   long long pairs = 0;
   std::vector<int> seen(n_kf, -1);
   for (int p = 0; p < n_points; p++) {
     const int s = point_obs_start[p], e1 = point_obs_start[p + 1];
-    if (e1 < s) return fail(SLAMGPU_EINVAL, "point_obs_start not monotone at %d", p);
+    if (e1 < s) return t_opt_err.fail(SLAMGPU_EINVAL, "point_obs_start not monotone at %d", p);
     long long m = 0;
     for (int e = s; e < e1; e++) {
       const int k = obs[e].keyframe;
       if (k < 0 || k >= n_kf)
-        return fail(SLAMGPU_EINVAL, "observation %d: keyframe %d outside [0, %d)", e, k, n_kf);
+        return t_opt_err.fail(SLAMGPU_EINVAL, "observation %d: keyframe %d outside [0, %d)", e, k, n_kf);
       if (obs[e].octave < 0 || obs[e].octave >= nlevels)
-        return fail(SLAMGPU_EINVAL, "observation %d: octave %d outside [0, %d)", e, obs[e].octave, nlevels);
-      if (seen[k] == p) return fail(SLAMGPU_EINVAL, "a map point is observed twice by one keyframe");
+        return t_opt_err.fail(SLAMGPU_EINVAL, "observation %d: octave %d outside [0, %d)", e, obs[e].octave, nlevels);
+      if (seen[k] == p) return t_opt_err.fail(SLAMGPU_EINVAL, "a map point is observed twice by one keyframe");
       seen[k] = p;
       m += free_of[k] >= 0;
     }
     pairs += m * (m + 1) / 2;
   }
-  if (pairs > (1ll << 30)) return fail(SLAMGPU_ECAP, "%s: %lld Schur pairs", what, pairs);
+  if (pairs > (1ll << 30)) return t_opt_err.fail(SLAMGPU_ECAP, "%s: %lld Schur pairs", what, pairs);
   // block profile of the reduced camera system: block row f spans block columns pfirst[f] .. f,
   // pfirst[f] = the smallest optimised keyframe sharing a map point with f (any observation: a
   // superset of every phase's active structure). Row i of S at S[prow[i] + k], k <= i.
@@ -452,43 +403,37 @@ int coop_host(const char* what, const slamgpu_camera* cam, const float* inv_sigm
   using clk = std::chrono::steady_clock;
   const auto t_host0 = clk::now();
   int dev = 0;
-  OPT_HIPCHECK(hipGetDevice(&dev));
+  HIPCHECK(t_opt_err, hipGetDevice(&dev));
   const int G = coop_grid(dev, K);
   size_t wsb = 0;
   coop_layout(nullptr, n_kf, n_points, n_obs, K, (int)pairs, G, pnnz, &wsb);
   // inputs and outputs in one region (one DMA each way through a pinned twin), then workspace
-  const size_t o_T = 0, o_mode = o_T + al256(64 * (size_t)n_kf);
-  const size_t o_pts = o_mode + al256(n_kf + 1), o_ps = o_pts + al256(12 * (size_t)n_points + 4);
-  const size_t o_obs = o_ps + al256(4 * ((size_t)n_points + 1));
-  const size_t o_free = o_obs + al256(sizeof(slamgpu_ba_obs) * (size_t)n_obs + 4);
-  const size_t o_kof = o_free + al256(4 * (size_t)n_kf + 4);
-  const size_t o_pf = o_kof + al256(4 * (size_t)K + 4);
-  const size_t o_prow = o_pf + al256(4 * (size_t)K + 4);
-  const size_t o_er = o_prow + al256(8 * 6 * (size_t)K + 8);
-  const size_t o_ctl = o_er + al256((size_t)n_obs + 4);
-  const size_t o_io = o_ctl + 256, o_ws = o_io;
-  HostStage& S = thread_stage();
-  if (int r = stage_reserve(S, o_ws + wsb)) return r;
-  if (S.pin_bytes < o_io) {
-    if (S.pin) OPT_HIPCHECK(hipHostFree(S.pin));
-    S.pin = nullptr;
-    S.pin_bytes = 0;
-    OPT_HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&S.pin), o_io, hipHostMallocDefault));
-    S.pin_bytes = o_io;
+  StageLease S(t_opt_err);
+  StageLayout L;
+  const CoopLayout l = layout_coop(L, n_kf, K, n_points, n_obs, wsb);
+  if (int r = S.reserve(L.size())) return r;
+  CoopExtras& X = coop_extras(S.device());
+  if (X.pin_bytes < l.io) {
+    if (X.pin) HIPCHECK(t_opt_err, hipHostFree(X.pin));
+    X.pin = nullptr;
+    X.pin_bytes = 0;
+    HIPCHECK(t_opt_err, hipHostMalloc(reinterpret_cast<void**>(&X.pin), l.io, hipHostMallocDefault));
+    X.pin_bytes = l.io;
   }
-  char* b = static_cast<char*>(S.buf);
-  char* h = S.pin;
+  char* b = S.at<char>(0);
+  char* h = X.pin;
+  hipStream_t st = S.stream();
   CoopSlots slots(dev, G, local ? stop_flag : nullptr);  // the device's coop residency budget
   if (slots.stopped()) {  // the LocalMapper aborted while the solve waited for slots
     for (int e = 0; e < n_obs; e++) erase[e] = 0;
     return 0;
   }
   static const bool prof = getenv("SLAMGPU_BA_PROFILE") != nullptr;
-  CoopWs w = coop_layout(b + o_ws, n_kf, n_points, n_obs, K, (int)pairs, G, pnnz, nullptr);
-  w.free_of_kf = reinterpret_cast<const int32_t*>(b + o_free);
-  w.kf_of_free = reinterpret_cast<const int32_t*>(b + o_kof);
-  w.pfirst = reinterpret_cast<const int32_t*>(b + o_pf);
-  w.prow = reinterpret_cast<const int64_t*>(b + o_prow);
+  CoopWs w = coop_layout(b + l.ws, n_kf, n_points, n_obs, K, (int)pairs, G, pnnz, nullptr);
+  w.free_of_kf = reinterpret_cast<const int32_t*>(b + l.free_of);
+  w.kf_of_free = reinterpret_cast<const int32_t*>(b + l.kf_of);
+  w.pfirst = reinterpret_cast<const int32_t*>(b + l.pfirst);
+  w.prow = reinterpret_cast<const int64_t*>(b + l.prow);
   if (!prof) w.prof = nullptr;
   w.na_max = na_max;
   {  // the grid factorisation wherever S takes the profile path (6K > 144): the one-hand-off
@@ -499,72 +444,72 @@ int coop_host(const char* what, const slamgpu_camera* cam, const float* inv_sigm
     const int mwg_env = e0 ? atoi(e0) : 1, mwg_min = e1 ? atoi(e1) : 0;
     w.mwg = mwg_env && K >= mwg_min;
   }
-  const CoopProblem pb{reinterpret_cast<const slamgpu_ba_obs*>(b + o_obs),
-                       reinterpret_cast<const int32_t*>(b + o_ps),
-                       reinterpret_cast<const uint8_t*>(b + o_mode),
-                       reinterpret_cast<float*>(b + o_T),
-                       reinterpret_cast<float*>(b + o_pts),
-                       local ? reinterpret_cast<uint8_t*>(b + o_er) : nullptr,
-                       reinterpret_cast<int32_t*>(b + o_ctl),
+  const CoopProblem pb{reinterpret_cast<const slamgpu_ba_obs*>(b + l.obs),
+                       reinterpret_cast<const int32_t*>(b + l.ps),
+                       reinterpret_cast<const uint8_t*>(b + l.mode),
+                       reinterpret_cast<float*>(b + l.T),
+                       reinterpret_cast<float*>(b + l.pts),
+                       local ? reinterpret_cast<uint8_t*>(b + l.er) : nullptr,
+                       reinterpret_cast<int32_t*>(b + l.ctl),
                        n_obs, n_points, n_kf, K};
   volatile int32_t* mirror = nullptr;
   if (stop_flag) {
-    if (!S.stop_host) {
+    if (!X.stop_host) {
       void* hm = nullptr;
-      OPT_HIPCHECK(hipHostMalloc(&hm, 64, hipHostMallocMapped | hipHostMallocCoherent));
-      S.stop_host = static_cast<int32_t*>(hm);
+      HIPCHECK(t_opt_err, hipHostMalloc(&hm, 64, hipHostMallocMapped | hipHostMallocCoherent));
+      X.stop_host = static_cast<int32_t*>(hm);
       void* d = nullptr;
-      OPT_HIPCHECK(hipHostGetDevicePointer(&d, hm, 0));
-      S.stop_dev = static_cast<int32_t*>(d);
+      HIPCHECK(t_opt_err, hipHostGetDevicePointer(&d, hm, 0));
+      X.stop_dev = static_cast<int32_t*>(d);
     }
-    mirror = S.stop_host;
+    mirror = X.stop_host;
   }
   // A barrier that gives up (CTL_ERR) leaves the caller's arrays untouched; when work-groups were
   // missing (never resident), the solve is staged and run once more before reporting.
   int32_t ctl[8];
   clk::time_point t_launch0, t_launch1, t_done;
   for (int attempt = 0;; attempt++) {
-    std::memcpy(h + o_T, kf_Tcw, 64 * (size_t)n_kf);
-    std::memcpy(h + o_mode, kf_mode, n_kf);
-    if (n_points) std::memcpy(h + o_pts, points, 12 * (size_t)n_points);
-    std::memcpy(h + o_ps, point_obs_start, 4 * ((size_t)n_points + 1));
-    if (n_obs) std::memcpy(h + o_obs, obs, sizeof(slamgpu_ba_obs) * (size_t)n_obs);
-    if (n_kf) std::memcpy(h + o_free, free_of.data(), 4 * (size_t)n_kf);
-    if (K) std::memcpy(h + o_kof, kf_of.data(), 4 * (size_t)K);
-    if (K) std::memcpy(h + o_pf, pfirst.data(), 4 * (size_t)K);
-    if (K) std::memcpy(h + o_prow, prow.data(), 8 * 6 * (size_t)K);
-    OPT_HIPCHECK(hipMemcpyAsync(b, h, o_er, hipMemcpyHostToDevice, S.stream));
+    std::memcpy(h + l.T, kf_Tcw, 64 * (size_t)n_kf);
+    std::memcpy(h + l.mode, kf_mode, n_kf);
+    if (n_points) std::memcpy(h + l.pts, points, 12 * (size_t)n_points);
+    std::memcpy(h + l.ps, point_obs_start, 4 * ((size_t)n_points + 1));
+    if (n_obs) std::memcpy(h + l.obs, obs, sizeof(slamgpu_ba_obs) * (size_t)n_obs);
+    if (n_kf) std::memcpy(h + l.free_of, free_of.data(), 4 * (size_t)n_kf);
+    if (K) std::memcpy(h + l.kf_of, kf_of.data(), 4 * (size_t)K);
+    if (K) std::memcpy(h + l.pfirst, pfirst.data(), 4 * (size_t)K);
+    if (K) std::memcpy(h + l.prow, prow.data(), 8 * 6 * (size_t)K);
+    HIPCHECK(t_opt_err, hipMemcpyAsync(b, h, l.er, hipMemcpyHostToDevice, st));
     if (mirror) *mirror = *stop_flag ? 1 : 0;
     t_launch0 = clk::now();
-    OPT_HIPCHECK(launch_coop_ba(P, pb, w, phases, n_phases, local,
-                                stop_flag ? S.stop_dev : nullptr, G, S.stream));
+    HIPCHECK(t_opt_err, launch_coop_ba(P, pb, w, phases, n_phases, local,
+                                stop_flag ? X.stop_dev : nullptr, G, st));
     // the outputs and the control words come back in the same region (pinned: asynchronous)
-    OPT_HIPCHECK(hipMemcpyAsync(h, b, o_io, hipMemcpyDeviceToHost, S.stream));
+    HIPCHECK(t_opt_err, hipMemcpyAsync(h, b, l.io, hipMemcpyDeviceToHost, st));
     t_launch1 = clk::now();
     // keep the device's view of the caller's flag live until the work is done
     if (mirror) {
       hipError_t q;
-      while ((q = hipStreamQuery(S.stream)) == hipErrorNotReady) {
+      while ((q = hipStreamQuery(st)) == hipErrorNotReady) {
         *mirror = *stop_flag ? 1 : 0;
         std::this_thread::sleep_for(std::chrono::microseconds(5));
       }
-      if (q != hipSuccess) return fail(SLAMGPU_EHIP, "%s: %s", what, hipGetErrorString(q));
+      if (q != hipSuccess) return t_opt_err.fail(SLAMGPU_EHIP, "%s: %s", what, hipGetErrorString(q));
     }
-    OPT_HIPCHECK(hipStreamSynchronize(S.stream));
+    HIPCHECK(t_opt_err, hipStreamSynchronize(st));
     t_done = clk::now();
-    std::memcpy(ctl, h + o_ctl, sizeof(ctl));
+    std::memcpy(ctl, h + l.ctl, sizeof(ctl));
     if (!ctl[CTL_ERR]) break;
     const bool missing = ctl[CTL_ARRIVED] < ctl[CTL_GRID] - 1;
     if (!missing || attempt > 0)
-      return fail(SLAMGPU_EDEVICE, "%s: grid barrier gave up after ~2 s without progress: %d of "
+      return t_opt_err.fail(SLAMGPU_EDEVICE, "%s: grid barrier gave up after ~2 s without progress: %d of "
                   "%d work-groups had arrived (%s)", what, ctl[CTL_ARRIVED], ctl[CTL_GRID],
                   missing ? "work-groups never became resident, twice" : "a work-group stalled");
     fprintf(stderr, "slamgpu %s: %d of %d work-groups resident at a grid barrier; retrying once\n",
             what, ctl[CTL_ARRIVED], ctl[CTL_GRID]);
   }
-  std::memcpy(kf_Tcw, h + o_T, 64 * (size_t)n_kf);
-  if (n_points) std::memcpy(points, h + o_pts, 12 * (size_t)n_points);
-  if (local && n_obs) std::memcpy(erase, h + o_er, n_obs);
+  std::memcpy(kf_Tcw, h + l.T, 64 * (size_t)n_kf);
+  if (n_points) std::memcpy(points, h + l.pts, 12 * (size_t)n_points);
+  if (local && n_obs) std::memcpy(erase, h + l.er, n_obs);
   if (prof) {
     auto us = [](clk::time_point a, clk::time_point b2) {
       return std::chrono::duration<double, std::micro>(b2 - a).count();
@@ -575,7 +520,7 @@ int coop_host(const char* what, const slamgpu_camera* cam, const float* inv_sigm
   if (lm_iterations) *lm_iterations = ctl[CTL_LM];
   if (w.prof) {  // SLAMGPU_BA_PROFILE: work-group 0's per-phase wall time
     double pr[16];
-    OPT_HIPCHECK(hipMemcpy(pr, w.prof, sizeof(pr), hipMemcpyDeviceToHost));
+    HIPCHECK(t_opt_err, hipMemcpy(pr, w.prof, sizeof(pr), hipMemcpyDeviceToHost));
     fprintf(stderr, "[%s] us: lin %.0f barrier %.0f assemble %.0f build_S %.0f factor %.0f "
             "kf_update %.0f points %.0f first-sync %.0f (G %d, K %d)\n", what, pr[0], pr[1],
             pr[2], pr[5], pr[6], pr[3], pr[4], pr[7], G, K);
@@ -616,7 +561,7 @@ int slamgpu_global_bundle_adjustment(const slamgpu_camera* cam, const float* inv
                                      float* points, int n_points, const int32_t* point_obs_start,
                                      const slamgpu_ba_obs* obs, int n_iterations, int robust,
                                      const volatile bool* stop_flag, int* lm_iterations) {
-  if (n_iterations < 0) return fail(SLAMGPU_EINVAL, "n_iterations %d < 0", n_iterations);
+  if (n_iterations < 0) return t_opt_err.fail(SLAMGPU_EINVAL, "n_iterations %d < 0", n_iterations);
   // optimizer.cpp:69-70 huber_thresh_2d = sqrt(5.99), huber_thresh_3d = sqrt(7.815) (float);
   // one optimize(num_iter) (:159-160)
   const CoopPhase ph[1] = {{n_iterations, robust ? 1 : 0, (double)(float)sqrt(5.99),
@@ -634,10 +579,10 @@ int slamgpu_optimize_sim3_device(const float K1[4], const float K2[4], const flo
   Sim3Params P;
   if (int r = make_sim3_params(K1, K2, inv_sigma2_1, inv_sigma2_2, nlevels, th2, fix_scale, &P))
     return r;
-  if (n_problems < 0) return fail(SLAMGPU_EINVAL, "n_problems %d < 0", n_problems);
+  if (n_problems < 0) return t_opt_err.fail(SLAMGPU_EINVAL, "n_problems %d < 0", n_problems);
   if (n_problems > 0 && (!d_match_start || !d_S12 || !d_n_inliers || !d_matches || !d_inlier))
-    return fail(SLAMGPU_EINVAL, "null device buffer");
-  OPT_HIPCHECK(launch_optimize_sim3(d_matches, d_match_start, n_problems, P, d_S12, d_inlier,
+    return t_opt_err.fail(SLAMGPU_EINVAL, "null device buffer");
+  HIPCHECK(t_opt_err, launch_optimize_sim3(d_matches, d_match_start, n_problems, P, d_S12, d_inlier,
                                     d_n_inliers, d_lm_iterations,
                                     static_cast<hipStream_t>(stream)));
   return 0;
@@ -651,34 +596,30 @@ int slamgpu_optimize_sim3(const float K1[4], const float K2[4], const float* inv
   if (int r = make_sim3_params(K1, K2, inv_sigma2_1, inv_sigma2_2, nlevels, th2, fix_scale, &P))
     return r;
   if (!S12 || !n_inliers || n < 0 || (n > 0 && (!matches || !inlier)))
-    return fail(SLAMGPU_EINVAL, "bad arguments");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "bad arguments");
   if (n > SLAMGPU_SIM3_MAX_MATCHES)
-    return fail(SLAMGPU_ECAP, "%d matches > SLAMGPU_SIM3_MAX_MATCHES (%d)", n,
+    return t_opt_err.fail(SLAMGPU_ECAP, "%d matches > SLAMGPU_SIM3_MAX_MATCHES (%d)", n,
                 SLAMGPU_SIM3_MAX_MATCHES);
   for (int i = 0; i < n; i++)
     if (matches[i].octave1 < 0 || matches[i].octave1 >= nlevels || matches[i].octave2 < 0 ||
         matches[i].octave2 >= nlevels)
-      return fail(SLAMGPU_EINVAL, "match %d: octave outside [0, %d)", i, nlevels);
-  HostStage& S = thread_stage();
-  const size_t off_m = 256, off_S = off_m + al256((size_t)n * sizeof(slamgpu_sim3_match));
-  const size_t off_i = off_S + 256, off_r = off_i + al256((size_t)n);
-  if (int r = stage_reserve(S, off_r + 256)) return r;
-  char* b = static_cast<char*>(S.buf);
+      return t_opt_err.fail(SLAMGPU_EINVAL, "match %d: octave outside [0, %d)", i, nlevels);
+  StageLease S(t_opt_err);
+  StageLayout L;
+  const SolveLayout l = layout_solve(L, n, sizeof(slamgpu_sim3_match), 8 * sizeof(double));
+  if (int r = S.reserve(L.size())) return r;
   const int32_t start[2] = {0, n};
-  OPT_HIPCHECK(hipMemcpyAsync(b, start, sizeof(start), hipMemcpyHostToDevice, S.stream));
-  if (n > 0)
-    OPT_HIPCHECK(hipMemcpyAsync(b + off_m, matches, (size_t)n * sizeof(slamgpu_sim3_match),
-                                hipMemcpyHostToDevice, S.stream));
-  OPT_HIPCHECK(hipMemcpyAsync(b + off_S, S12, 8 * sizeof(double), hipMemcpyHostToDevice, S.stream));
-  OPT_HIPCHECK(launch_optimize_sim3(
-      reinterpret_cast<const slamgpu_sim3_match*>(b + off_m), reinterpret_cast<int32_t*>(b), 1, P,
-      reinterpret_cast<double*>(b + off_S), reinterpret_cast<uint8_t*>(b + off_i),
-      reinterpret_cast<int32_t*>(b + off_r), nullptr, S.stream));
+  HIPCHECK(t_opt_err, S.upload(l.start, start, sizeof(start)));
+  HIPCHECK(t_opt_err, S.upload(l.items, matches, (size_t)n * sizeof(slamgpu_sim3_match)));
+  HIPCHECK(t_opt_err, S.upload(l.state, S12, 8 * sizeof(double)));
+  HIPCHECK(t_opt_err, launch_optimize_sim3(
+      S.at<slamgpu_sim3_match>(l.items), S.at<int32_t>(l.start), 1, P, S.at<double>(l.state),
+      S.at<uint8_t>(l.flags), S.at<int32_t>(l.result), nullptr, S.stream()));
   int32_t res = 0;
-  OPT_HIPCHECK(hipMemcpyAsync(&res, b + off_r, sizeof(res), hipMemcpyDeviceToHost, S.stream));
-  OPT_HIPCHECK(hipMemcpyAsync(S12, b + off_S, 8 * sizeof(double), hipMemcpyDeviceToHost, S.stream));
-  if (n > 0) OPT_HIPCHECK(hipMemcpyAsync(inlier, b + off_i, n, hipMemcpyDeviceToHost, S.stream));
-  OPT_HIPCHECK(hipStreamSynchronize(S.stream));
+  HIPCHECK(t_opt_err, S.download(&res, l.result, sizeof(res)));
+  HIPCHECK(t_opt_err, S.download(S12, l.state, 8 * sizeof(double)));
+  HIPCHECK(t_opt_err, S.download(inlier, l.flags, (size_t)n));
+  HIPCHECK(t_opt_err, hipStreamSynchronize(S.stream()));
   *n_inliers = res;
   return 0;
 }
@@ -689,19 +630,19 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
                                      const int32_t* point_ref, int n_points, int* lm_iterations) {
   if (lm_iterations) *lm_iterations = 0;
   if (n_kf < 0 || n_edges < 0 || n_points < 0 || n_iterations < 0)
-    return fail(SLAMGPU_EINVAL, "negative sizes");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "negative sizes");
   if ((n_kf > 0 && (!Scw || !fixed)) || (n_edges > 0 && !edges) ||
       (n_points > 0 && points && !point_ref))
-    return fail(SLAMGPU_EINVAL, "null buffer");
+    return t_opt_err.fail(SLAMGPU_EINVAL, "null buffer");
   for (int k = 0; k < n_edges; k++)
     if (edges[k].i < 0 || edges[k].i >= n_kf || edges[k].j < 0 || edges[k].j >= n_kf ||
         edges[k].i == edges[k].j)
-      return fail(SLAMGPU_EINVAL, "edge %d: keyframes (%d, %d) invalid for %d keyframes", k,
+      return t_opt_err.fail(SLAMGPU_EINVAL, "edge %d: keyframes (%d, %d) invalid for %d keyframes", k,
                   edges[k].i, edges[k].j, n_kf);
   if (points)
     for (int q = 0; q < n_points; q++)
       if (point_ref[q] < 0 || point_ref[q] >= n_kf)
-        return fail(SLAMGPU_EINVAL, "point %d: reference keyframe %d outside [0, %d)", q,
+        return t_opt_err.fail(SLAMGPU_EINVAL, "point %d: reference keyframe %d outside [0, %d)", q,
                     point_ref[q], n_kf);
   if (n_kf == 0) return 0;
   // ---- the graph's structure (host): free vertices, profile, assembly targets, extents ----
@@ -768,50 +709,42 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
   }
   // ---- one device region: inputs, structure, state ----
   const size_t E = (size_t)n_edges, N = (size_t)n_kf, P7 = 7 * (size_t)F;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o += al256(bytes + 1);
-    return at;
-  };
-  const size_t o_edges = take(E * sizeof(slamgpu_sim3_edge)), o_fidx = take(4 * N);
-  const size_t o_start = take(4 * (size_t)F), o_off = take(8 * ((size_t)F + 1));
-  const size_t o_tb = take(4 * (size_t)n_targets), o_tv = take(4 * (size_t)n_targets);
-  const size_t o_tp = take(4 * ((size_t)n_targets + 1)), o_ti = take(4 * tgt_items.size());
-  const size_t o_ep = take(4 * ((size_t)F + 1)), o_er = take(4 * ext_rows.size());
-  const size_t o_eb = take(8 * ext_base.size());
-  const size_t o_S = take(8 * 8 * N), o_S2 = take(8 * 8 * N), o_S0 = take(8 * 8 * N);
-  const size_t o_err = take(8 * 7 * E), o_chi = take(8 * E), o_con = take(8 * kEgContrib * E);
-  const size_t o_J = take(8 * 98 * E);
-  const size_t o_H = take(8 * 49 * (size_t)n_blocks), o_b = take(8 * P7);
-  const size_t o_L = take(8 * 49 * (size_t)n_blocks), o_x = take(8 * P7), o_y = take(8 * P7);
-  const size_t o_out = take(64), o_T = take(Tcw ? 64 * N : 0);
-  const size_t o_pts = take(points ? 12 * (size_t)n_points : 0);
-  const size_t o_ref = take(points ? 4 * (size_t)n_points : 0);
-  HostStage& HS = thread_stage();
-  if (int r = stage_reserve(HS, o)) return r;
-  char* d = static_cast<char*>(HS.buf);
-  hipStream_t st = HS.stream;
-  auto up = [&](size_t at, const void* src, size_t bytes) -> hipError_t {
-    return bytes ? hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
-  OPT_HIPCHECK(up(o_edges, edges, E * sizeof(slamgpu_sim3_edge)));
-  OPT_HIPCHECK(up(o_fidx, fidx.data(), 4 * N));
-  OPT_HIPCHECK(up(o_start, start.data(), 4 * (size_t)F));
-  OPT_HIPCHECK(up(o_off, off.data(), 8 * ((size_t)F + 1)));
-  OPT_HIPCHECK(up(o_tb, tgt_block.data(), 4 * (size_t)n_targets));
-  OPT_HIPCHECK(up(o_tv, tgt_vertex.data(), 4 * (size_t)n_targets));
-  OPT_HIPCHECK(up(o_tp, tgt_ptr.data(), 4 * ((size_t)n_targets + 1)));
-  OPT_HIPCHECK(up(o_ti, tgt_items.data(), 4 * tgt_items.size()));
-  OPT_HIPCHECK(up(o_ep, ext_ptr.data(), 4 * ((size_t)F + 1)));
-  OPT_HIPCHECK(up(o_er, ext_rows.data(), 4 * ext_rows.size()));
-  OPT_HIPCHECK(up(o_eb, ext_base.data(), 8 * ext_base.size()));
-  OPT_HIPCHECK(up(o_S, Scw, 64 * N));
-  OPT_HIPCHECK(up(o_S0, Scw, 64 * N));
-  OPT_HIPCHECK(hipMemsetAsync(d + o_x, 0, 8 * P7 + 1, st));
+  StageLease HS(t_opt_err);
+  StageLayout L;
+  const size_t o_edges = L.take(E * sizeof(slamgpu_sim3_edge)), o_fidx = L.take(4 * N);
+  const size_t o_start = L.take(4 * (size_t)F), o_off = L.take(8 * ((size_t)F + 1));
+  const size_t o_tb = L.take(4 * (size_t)n_targets), o_tv = L.take(4 * (size_t)n_targets);
+  const size_t o_tp = L.take(4 * ((size_t)n_targets + 1)), o_ti = L.take(4 * tgt_items.size());
+  const size_t o_ep = L.take(4 * ((size_t)F + 1)), o_er = L.take(4 * ext_rows.size());
+  const size_t o_eb = L.take(8 * ext_base.size());
+  const size_t o_S = L.take(8 * 8 * N), o_S2 = L.take(8 * 8 * N), o_S0 = L.take(8 * 8 * N);
+  const size_t o_err = L.take(8 * 7 * E), o_chi = L.take(8 * E), o_con = L.take(8 * kEgContrib * E);
+  const size_t o_J = L.take(8 * 98 * E);
+  const size_t o_H = L.take(8 * 49 * (size_t)n_blocks), o_b = L.take(8 * P7);
+  const size_t o_L = L.take(8 * 49 * (size_t)n_blocks), o_x = L.take(8 * P7), o_y = L.take(8 * P7);
+  const size_t o_out = L.take(64), o_T = L.take(Tcw ? 64 * N : 0);
+  const size_t o_pts = L.take(points ? 12 * (size_t)n_points : 0);
+  const size_t o_ref = L.take(points ? 4 * (size_t)n_points : 0);
+  if (int r = HS.reserve(L.size())) return r;
+  char* d = HS.at<char>(0);
+  hipStream_t st = HS.stream();
+  HIPCHECK(t_opt_err, HS.upload(o_edges, edges, E * sizeof(slamgpu_sim3_edge)));
+  HIPCHECK(t_opt_err, HS.upload(o_fidx, fidx.data(), 4 * N));
+  HIPCHECK(t_opt_err, HS.upload(o_start, start.data(), 4 * (size_t)F));
+  HIPCHECK(t_opt_err, HS.upload(o_off, off.data(), 8 * ((size_t)F + 1)));
+  HIPCHECK(t_opt_err, HS.upload(o_tb, tgt_block.data(), 4 * (size_t)n_targets));
+  HIPCHECK(t_opt_err, HS.upload(o_tv, tgt_vertex.data(), 4 * (size_t)n_targets));
+  HIPCHECK(t_opt_err, HS.upload(o_tp, tgt_ptr.data(), 4 * ((size_t)n_targets + 1)));
+  HIPCHECK(t_opt_err, HS.upload(o_ti, tgt_items.data(), 4 * tgt_items.size()));
+  HIPCHECK(t_opt_err, HS.upload(o_ep, ext_ptr.data(), 4 * ((size_t)F + 1)));
+  HIPCHECK(t_opt_err, HS.upload(o_er, ext_rows.data(), 4 * ext_rows.size()));
+  HIPCHECK(t_opt_err, HS.upload(o_eb, ext_base.data(), 8 * ext_base.size()));
+  HIPCHECK(t_opt_err, HS.upload(o_S, Scw, 64 * N));
+  HIPCHECK(t_opt_err, HS.upload(o_S0, Scw, 64 * N));
+  HIPCHECK(t_opt_err, hipMemsetAsync(d + o_x, 0, 8 * P7 + 1, st));
   if (points) {
-    OPT_HIPCHECK(up(o_pts, points, 12 * (size_t)n_points));
-    OPT_HIPCHECK(up(o_ref, point_ref, 4 * (size_t)n_points));
+    HIPCHECK(t_opt_err, HS.upload(o_pts, points, 12 * (size_t)n_points));
+    HIPCHECK(t_opt_err, HS.upload(o_ref, point_ref, 4 * (size_t)n_points));
   }
   EgGraph G;
   G.n = n_kf;
@@ -854,11 +787,11 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
   double lambda = 1e-16;  // setUserLambdaInit(1e-16) (:732)
   int ni = 2, nbad = 0, its = 0;
   for (int it = 0; it < n_iterations && F > 0; it++) {
-    OPT_HIPCHECK(launch_eg_linearize(G, W, st));
-    OPT_HIPCHECK(launch_eg_chi2_sum(G, W, st));
-    OPT_HIPCHECK(launch_eg_assemble(G, W, n_blocks, st));
+    HIPCHECK(t_opt_err, launch_eg_linearize(G, W, st));
+    HIPCHECK(t_opt_err, launch_eg_chi2_sum(G, W, st));
+    HIPCHECK(t_opt_err, launch_eg_assemble(G, W, n_blocks, st));
     double h[3];
-    OPT_HIPCHECK(read_out(h));
+    HIPCHECK(t_opt_err, read_out(h));
     double currentChi = h[0];
     const double iniChi = currentChi;
     if (it == 0) {
@@ -869,11 +802,11 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
     double rho = 0;
     int qmax = 0;
     do {
-      OPT_HIPCHECK(launch_eg_factor_solve(G, W, n_blocks, lambda, st));
-      OPT_HIPCHECK(launch_eg_update(G, W, st));
-      OPT_HIPCHECK(launch_eg_errors(G, W.S_trial, W, st));
-      OPT_HIPCHECK(launch_eg_chi2_sum(G, W, st));
-      OPT_HIPCHECK(read_out(h));
+      HIPCHECK(t_opt_err, launch_eg_factor_solve(G, W, n_blocks, lambda, st));
+      HIPCHECK(t_opt_err, launch_eg_update(G, W, st));
+      HIPCHECK(t_opt_err, launch_eg_errors(G, W.S_trial, W, st));
+      HIPCHECK(t_opt_err, launch_eg_chi2_sum(G, W, st));
+      HIPCHECK(t_opt_err, read_out(h));
       double tempChi = h[0];
       if (h[2] == 0.0) tempChi = DBL_MAX;
       rho = (currentChi - tempChi) / (h[1] + 1e-3);
@@ -896,15 +829,15 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
     else nbad = 0;
     if (nbad >= 3) break;
   }
-  OPT_HIPCHECK(launch_eg_finish(G, W.S, reinterpret_cast<double*>(d + o_S0),
+  HIPCHECK(t_opt_err, launch_eg_finish(G, W.S, reinterpret_cast<double*>(d + o_S0),
                                 Tcw ? reinterpret_cast<float*>(d + o_T) : nullptr,
                                 points ? reinterpret_cast<float*>(d + o_pts) : nullptr,
                                 reinterpret_cast<const int32_t*>(d + o_ref), n_points, st));
-  OPT_HIPCHECK(hipMemcpyAsync(Scw, W.S, 64 * N, hipMemcpyDeviceToHost, st));
-  if (Tcw) OPT_HIPCHECK(hipMemcpyAsync(Tcw, d + o_T, 64 * N, hipMemcpyDeviceToHost, st));
+  HIPCHECK(t_opt_err, hipMemcpyAsync(Scw, W.S, 64 * N, hipMemcpyDeviceToHost, st));
+  if (Tcw) HIPCHECK(t_opt_err, hipMemcpyAsync(Tcw, d + o_T, 64 * N, hipMemcpyDeviceToHost, st));
   if (points && n_points)
-    OPT_HIPCHECK(hipMemcpyAsync(points, d + o_pts, 12 * (size_t)n_points, hipMemcpyDeviceToHost, st));
-  OPT_HIPCHECK(hipStreamSynchronize(st));
+    HIPCHECK(t_opt_err, hipMemcpyAsync(points, d + o_pts, 12 * (size_t)n_points, hipMemcpyDeviceToHost, st));
+  HIPCHECK(t_opt_err, hipStreamSynchronize(st));
   if (lm_iterations) *lm_iterations = its;
   return 0;
 }

@@ -8,7 +8,6 @@
 // OrbMatcher::SearchByProjection (orb_matcher.cpp:13, :1312).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -16,6 +15,7 @@
 #include <vector>
 
 #include "../../include/slamgpu.h"
+#include "host_common.h"
 #include "match_kernels.h"
 #include "undistort.h"
 #include "orb_kernels.h"
@@ -37,7 +37,7 @@ struct slamgpu_ctx {
   OrbTables tables{};
   OrbGeom geom{};
   int max_frames = 0, max_images = 0;
-  std::string err;
+  ErrorSlot err;  // slamgpu_last_error(ctx)
   // device geometry
   OrbGeom* d_geom = nullptr;
   ResizeX* d_rx = nullptr;
@@ -111,34 +111,12 @@ struct TimerScope {
   ~TimerScope() { g_timer = prev; }
 };
 
-static int fail(slamgpu_ctx* c, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  if (c) c->err = buf;
-  return code;
+// Where a call on context c reports: the context's slot (calls that validate a NULL context drop
+// the message).
+static ErrorSlot& slot(slamgpu_ctx* c) {
+  static thread_local ErrorSlot none;
+  return c ? c->err : none;
 }
-
-// Why the last slamgpu_create on this thread failed (no context exists to hold the message).
-thread_local std::string t_create_err;
-static int create_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  t_create_err = buf;
-  return code;
-}
-
-#define HIPCHECK(c, x)                                                                 \
-  do {                                                                                 \
-    hipError_t e_ = (x);                                                               \
-    if (e_ != hipSuccess)                                                              \
-      return fail(c, SLAMGPU_EHIP, "%s failed: %s", #x, hipGetErrorString(e_));        \
-  } while (0)
 
 template <typename T>
 static int dalloc(slamgpu_ctx* c, T** p, size_t count) {
@@ -146,14 +124,14 @@ static int dalloc(slamgpu_ctx* c, T** p, size_t count) {
   const size_t bytes = count * sizeof(T) + 256;
   hipError_t e = hipMalloc(&q, bytes);
   if (e != hipSuccess)
-    return fail(c, SLAMGPU_EHIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    return slot(c).fail(SLAMGPU_EHIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
   c->allocs.push_back(q);
   *p = static_cast<T*>(q);
   return 0;
 }
 
 static int hcheck(slamgpu_ctx* c, hipError_t e) {
-  return e == hipSuccess ? 0 : fail(c, SLAMGPU_EHIP, "HIP error: %s", hipGetErrorString(e));
+  return e == hipSuccess ? 0 : slot(c).fail(SLAMGPU_EHIP, "HIP error: %s", hipGetErrorString(e));
 }
 
 static hipStream_t pick_stream(slamgpu_ctx* c, void* s) {
@@ -227,10 +205,10 @@ static int round_up_cells(int n) { return (n + kCellGroup - 1) / kCellGroup * kC
 
 static int check_device_err(slamgpu_ctx* c) {
   uint32_t e = 0;
-  HIPCHECK(c, hipMemcpy(&e, c->ws.err, sizeof(e), hipMemcpyDeviceToHost));
+  HIPCHECK(c->err, hipMemcpy(&e, c->ws.err, sizeof(e), hipMemcpyDeviceToHost));
   if (e) {
     (void)hipMemset(c->ws.err, 0, sizeof(uint32_t));
-    return fail(c, SLAMGPU_EDEVICE, "device capacity overflow (bits 0x%x)", e);
+    return slot(c).fail(SLAMGPU_EDEVICE, "device capacity overflow (bits 0x%x)", e);
   }
   return 0;
 }
@@ -266,13 +244,13 @@ int slamgpu_create(int device, const slamgpu_orb_params* p, int cols, int rows, 
         "unsupported Gaussian kernel",
         "a level's octree nodes overflow octree_lvl_kernel's LDS budget"};
     delete c;
-    return create_fail(SLAMGPU_EINVAL, "slamgpu_create(%dx%d, nlevels %d, scale %g): %s", cols,
+    return t_create_err.fail(SLAMGPU_EINVAL, "slamgpu_create(%dx%d, nlevels %d, scale %g): %s", cols,
                        rows, p->nlevels, (double)p->scale_factor,
                        why[std::min(std::max(-gr, 0), 7)]);
   }
   if (!extract_build_matches(c->geom)) {
     delete c;
-    return create_fail(SLAMGPU_EINVAL,
+    return t_create_err.fail(SLAMGPU_EINVAL,
                        "slamgpu_create: orb_geometry.cpp and orb_kernels.hip were built with "
                        "different PYR_RING_STRIP / FAST_CELLS_PER_WAVE");
   }
@@ -280,14 +258,14 @@ int slamgpu_create(int device, const slamgpu_orb_params* p, int cols, int rows, 
   if (c->geom.kp_cap > 4096) {  // matcher keys carry a 12-bit keypoint index
     const int kpc = c->geom.kp_cap;
     delete c;
-    return create_fail(SLAMGPU_EINVAL, "slamgpu_create: nfeatures %d gives %d keypoints per image "
+    return t_create_err.fail(SLAMGPU_EINVAL, "slamgpu_create: nfeatures %d gives %d keypoints per image "
                        "> 4096", p->nfeatures, kpc);
   }
   for (int l = 0; l < c->geom.nlevels; l++)
     if (c->geom.lv[l].node_cap > 1024) {
       const int need = c->geom.lv[l].node_cap;
       delete c;
-      return create_fail(SLAMGPU_EINVAL, "slamgpu_create: level %d needs %d octree nodes > 1024",
+      return t_create_err.fail(SLAMGPU_EINVAL, "slamgpu_create: level %d needs %d octree nodes > 1024",
                          l, need);  // octree LDS arrays hold <= 2048 list nodes
     }
   c->device = device;
@@ -304,10 +282,10 @@ int slamgpu_create(int device, const slamgpu_orb_params* p, int cols, int rows, 
       return rc;                         \
     }                                    \
   } while (0)
-  TRY(hipSetDevice(device) == hipSuccess ? 0 : fail(c, SLAMGPU_EHIP, "hipSetDevice"));
+  TRY(hipSetDevice(device) == hipSuccess ? 0 : slot(c).fail(SLAMGPU_EHIP, "hipSetDevice"));
   TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess
           ? 0
-          : fail(c, SLAMGPU_EHIP, "hipStreamCreate"));
+          : slot(c).fail(SLAMGPU_EHIP, "hipStreamCreate"));
   {  // the side stream of launch_extract's level-0 FAST (SLAMGPU_FORK=0 disables it)
     const char* e = getenv("SLAMGPU_FORK");
     const int mode = e ? atoi(e) : 1;
@@ -319,7 +297,7 @@ int slamgpu_create(int device, const slamgpu_orb_params* p, int cols, int rows, 
                   hipEventCreateWithFlags(&fx.fork1, hipEventDisableTiming) == hipSuccess &&
                   hipEventCreateWithFlags(&fx.join1, hipEventDisableTiming) == hipSuccess
               ? 0
-              : fail(c, SLAMGPU_EHIP, "side stream / events"));
+              : slot(c).fail(SLAMGPU_EHIP, "side stream / events"));
   }
   const OrbGeom& g = c->geom;
   const int n = c->max_images;
@@ -452,8 +430,8 @@ static int run_frontend(slamgpu_ctx* c, const ImageBatch& b, int n_frames, int n
     const bool fork = fx.side0 && fx.fork1 && fx.join1 && n_frames > 8;
     hipStream_t gs = fork ? fx.side0 : st;
     if (fork) {
-      HIPCHECK(c, hipEventRecord(fx.fork1, st));
-      HIPCHECK(c, hipStreamWaitEvent(gs, fx.fork1, 0));
+      HIPCHECK(c->err, hipEventRecord(fx.fork1, st));
+      HIPCHECK(c->err, hipStreamWaitEvent(gs, fx.fork1, 0));
     }
     if (c->dist_on)
       launch_undistort(FrameKps{c->out.kps, c->out.desc, c->out.nkps, 2 * (int64_t)c->geom.kp_cap, 2},
@@ -472,11 +450,11 @@ static int run_frontend(slamgpu_ctx* c, const ImageBatch& b, int n_frames, int n
     }
     launch_stereo(b, g, c->cam, n_frames, c->sws, c->sout, st, pack, aux);
     if (fork) {
-      HIPCHECK(c, hipEventRecord(fx.join1, gs));
-      HIPCHECK(c, hipStreamWaitEvent(st, fx.join1, 0));
+      HIPCHECK(c->err, hipEventRecord(fx.join1, gs));
+      HIPCHECK(c->err, hipStreamWaitEvent(st, fx.join1, 0));
     }
   }
-  HIPCHECK(c, hipGetLastError());
+  HIPCHECK(c->err, hipGetLastError());
   return 0;
 }
 
@@ -497,7 +475,7 @@ static void stage_host(slamgpu_ctx* c, const uint8_t* const* imgs, int n, size_t
 }
 static int stage_images(slamgpu_ctx* c, const uint8_t* const* imgs, int n, size_t step) {
   stage_host(c, imgs, n, step);
-  HIPCHECK(c, hipMemcpyAsync(c->d_in, c->h_in, (size_t)n * c->in_stride, hipMemcpyHostToDevice,
+  HIPCHECK(c->err, hipMemcpyAsync(c->d_in, c->h_in, (size_t)n * c->in_stride, hipMemcpyHostToDevice,
                              c->stream));
   return 0;
 }
@@ -519,7 +497,7 @@ static int stage_images_pipelined(slamgpu_ctx* c, const uint8_t* const* imgs, in
           std::memcpy(dst + (int64_t)y * pitch, imgs[i] + y * step, cols);
       }
       const size_t off = (size_t)i * c->in_stride + (size_t)y0 * pitch;
-      HIPCHECK(c, hipMemcpyAsync(c->d_in + off, c->h_in + off, (size_t)(y1 - y0) * pitch,
+      HIPCHECK(c->err, hipMemcpyAsync(c->d_in + off, c->h_in + off, (size_t)(y1 - y0) * pitch,
                                  hipMemcpyHostToDevice, c->stream));
     }
   }
@@ -529,12 +507,12 @@ static int stage_images_pipelined(slamgpu_ctx* c, const uint8_t* const* imgs, in
 int slamgpu_extract(slamgpu_ctx* c, const uint8_t* img, size_t step, slamgpu_keypoint* kps,
                     uint8_t* desc, int cap, int* n_out) {
   if (!c || !img) return SLAMGPU_EINVAL;
-  HIPCHECK(c, hipSetDevice(c->device));
+  HIPCHECK(c->err, hipSetDevice(c->device));
   if (int r = stage_images(c, &img, 1, step)) return r;
   ImageBatch b{c->d_in, c->d_in + c->in_stride, 2 * c->in_stride, c->in_pitch, c->d_pyr};
   int rc = run_frontend(c, b, 1, 1, false, c->stream);
   if (rc) return rc;
-  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  HIPCHECK(c->err, hipStreamSynchronize(c->stream));
   if ((rc = check_device_err(c))) return rc;
   return slamgpu_download_keypoints(c, 0, kps, desc, cap, n_out);
 }
@@ -556,8 +534,8 @@ int slamgpu_get_pyramid_level(slamgpu_ctx* c, int img, int level, uint8_t* dst, 
     src = c->d_pyr + (int64_t)img * c->geom.pyr_bytes + L.offset;
     pitch = L.pitch;
   }
-  HIPCHECK(c, hipStreamSynchronize(c->stream));
-  HIPCHECK(c, hipMemcpy2D(dst, dst_step, src, pitch, L.w, L.h, hipMemcpyDeviceToHost));
+  HIPCHECK(c->err, hipStreamSynchronize(c->stream));
+  HIPCHECK(c->err, hipMemcpy2D(dst, dst_step, src, pitch, L.w, L.h, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -565,7 +543,7 @@ int slamgpu_debug_level_keys(slamgpu_ctx* c, int img, int level, int stage, uint
                              int cap, int* n_out) {
   if (!c || img < 0 || img >= c->n_images_last || level < 0 || level >= c->geom.nlevels)
     return SLAMGPU_EINVAL;
-  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  HIPCHECK(c->err, hipStreamSynchronize(c->stream));
   const OrbGeom& g = c->geom;
   const LevelGeom& L = g.lv[level];
   std::vector<uint32_t> out;
@@ -573,12 +551,12 @@ int slamgpu_debug_level_keys(slamgpu_ctx* c, int img, int level, int stage, uint
     const int ncell = L.ncols * L.nrows;
     std::vector<int> cnt(ncell);
     const int64_t cb = (int64_t)img * g.cells_per_image + L.cell_base;
-    HIPCHECK(c, hipMemcpy(cnt.data(), c->ws.cell_count + cb, sizeof(int) * ncell,
+    HIPCHECK(c->err, hipMemcpy(cnt.data(), c->ws.cell_count + cb, sizeof(int) * ncell,
                           hipMemcpyDeviceToHost));
     // the level's key slots at once; a cell's keys follow its group's earlier cells
     // (kCellGroup, fast_cells_kernel)
     std::vector<uint32_t> keys((size_t)round_up_cells(ncell) * g.cell_cap);
-    HIPCHECK(c, hipMemcpy(keys.data(), c->ws.cell_keys + cb * g.cell_cap,
+    HIPCHECK(c->err, hipMemcpy(keys.data(), c->ws.cell_keys + cb * g.cell_cap,
                           sizeof(uint32_t) * keys.size(), hipMemcpyDeviceToHost));
     int gfill = 0;
     for (int i = 0; i < ncell; i++) {
@@ -589,15 +567,15 @@ int slamgpu_debug_level_keys(slamgpu_ctx* c, int img, int level, int stage, uint
     }
   } else {
     int n = 0;
-    HIPCHECK(c, hipMemcpy(&n, c->ws.oct_count + img * g.nlevels + level, sizeof(int),
+    HIPCHECK(c->err, hipMemcpy(&n, c->ws.oct_count + img * g.nlevels + level, sizeof(int),
                           hipMemcpyDeviceToHost));
     out.resize(n);
     if (n)
-      HIPCHECK(c, hipMemcpy(out.data(), c->ws.oct_keys + (int64_t)img * g.out_per_image + L.out_base,
+      HIPCHECK(c->err, hipMemcpy(out.data(), c->ws.oct_keys + (int64_t)img * g.out_per_image + L.out_base,
                             sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
   }
   if (n_out) *n_out = (int)out.size();
-  if ((int)out.size() > cap) return fail(c, SLAMGPU_ECAP, "need %zu keys", out.size());
+  if ((int)out.size() > cap) return slot(c).fail(SLAMGPU_ECAP, "need %zu keys", out.size());
   if (keys && !out.empty()) std::memcpy(keys, out.data(), out.size() * sizeof(uint32_t));
   return 0;
 }
@@ -608,7 +586,7 @@ int slamgpu_debug_level_keys(slamgpu_ctx* c, int img, int level, int stage, uint
 static int enqueue_frame_stereo(slamgpu_ctx* c) {
   ImageBatch b{c->d_in, c->d_in + c->in_stride, 2 * c->in_stride, c->in_pitch, c->d_pyr};
   if (int rc = run_frontend(c, b, 1, 2, true, c->stream, c->d_res)) return rc;
-  HIPCHECK(c, hipMemcpyAsync(c->h_res, c->d_res, res_mirror_bytes(c->geom.kp_cap),
+  HIPCHECK(c->err, hipMemcpyAsync(c->h_res, c->d_res, res_mirror_bytes(c->geom.kp_cap),
                              hipMemcpyDeviceToHost, c->stream));
   return 0;
 }
@@ -641,19 +619,19 @@ static int launch_frame_graph(slamgpu_ctx* c) {
                     std::memcmp(&c->fdist, &c->dist, sizeof(Distortion)) == 0;
   if (!same) {
     drop_frame_graph(c);
-    HIPCHECK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+    HIPCHECK(c->err, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
     const int rc = enqueue_frame_stereo(c);
     hipGraph_t g = nullptr;
     const hipError_t e = hipStreamEndCapture(c->stream, &g);
     if (rc || e != hipSuccess) {
       if (g) (void)hipGraphDestroy(g);
-      return rc ? rc : fail(c, SLAMGPU_EHIP, "frame graph capture: %s", hipGetErrorString(e));
+      return rc ? rc : slot(c).fail(SLAMGPU_EHIP, "frame graph capture: %s", hipGetErrorString(e));
     }
     const hipError_t ei = hipGraphInstantiate(&c->fexec, g, nullptr, nullptr, 0);
     if (ei != hipSuccess) {
       (void)hipGraphDestroy(g);
       c->fexec = nullptr;
-      return fail(c, SLAMGPU_EHIP, "frame graph instantiate: %s", hipGetErrorString(ei));
+      return slot(c).fail(SLAMGPU_EHIP, "frame graph instantiate: %s", hipGetErrorString(ei));
     }
     c->fgraph = g;
     c->fcam = c->cam;
@@ -665,14 +643,14 @@ static int launch_frame_graph(slamgpu_ctx* c) {
     c->n_frames_last = 1;
     c->n_images_last = 2;
   }
-  HIPCHECK(c, hipGraphLaunch(c->fexec, c->stream));
+  HIPCHECK(c->err, hipGraphLaunch(c->fexec, c->stream));
   return 0;
 }
 
 int slamgpu_frame_stereo(slamgpu_ctx* c, const uint8_t* left, const uint8_t* right, size_t step,
                          const slamgpu_camera* cam) {
   if (!c || !left || !right || !cam) return SLAMGPU_EINVAL;
-  HIPCHECK(c, hipSetDevice(c->device));
+  HIPCHECK(c->err, hipSetDevice(c->device));
   set_camera(c, cam);
   const uint8_t* imgs[2] = {left, right};
   if (int r = stage_images_pipelined(c, imgs, 2, step)) return r;
@@ -680,12 +658,12 @@ int slamgpu_frame_stereo(slamgpu_ctx* c, const uint8_t* left, const uint8_t* rig
   const int rc = frame_graph_enabled() && !c->timer.on ? launch_frame_graph(c)
                                                        : enqueue_frame_stereo(c);
   if (rc) return rc;
-  HIPCHECK(c, hipStreamSynchronize(c->stream));
+  HIPCHECK(c->err, hipStreamSynchronize(c->stream));
   const ResMirror m = res_mirror(c);
   if (m.err[0] | m.err[1]) {  // the error word as the two packing kernels saw it
     const uint32_t e = m.err[0] | m.err[1];
     (void)hipMemset(c->ws.err, 0, sizeof(uint32_t));
-    return fail(c, SLAMGPU_EDEVICE, "device capacity overflow (bits 0x%x)", e);
+    return slot(c).fail(SLAMGPU_EDEVICE, "device capacity overflow (bits 0x%x)", e);
   }
   c->res_valid = true;
   return 0;
@@ -696,7 +674,7 @@ int slamgpu_frontend_device(slamgpu_ctx* c, const uint8_t* d_left, const uint8_t
                             const slamgpu_camera* cam, void* stream) {
   if (!c || !d_left || !d_right || !cam || n_frames < 1 || n_frames > c->max_frames ||
       pitch < (size_t)c->geom.cols)
-    return fail(c, SLAMGPU_EINVAL, "slamgpu_frontend_device: bad arguments");
+    return slot(c).fail(SLAMGPU_EINVAL, "slamgpu_frontend_device: bad arguments");
   set_camera(c, cam);
   ImageBatch b{d_left, d_right, (int64_t)frame_stride, (int)pitch, c->d_pyr};
   return run_frontend(c, b, n_frames, 2 * n_frames, true, pick_stream(c, stream));
@@ -704,7 +682,7 @@ int slamgpu_frontend_device(slamgpu_ctx* c, const uint8_t* d_left, const uint8_t
 
 int slamgpu_sync(slamgpu_ctx* c, void* stream) {
   if (!c) return SLAMGPU_EINVAL;
-  HIPCHECK(c, hipStreamSynchronize(pick_stream(c, stream)));
+  HIPCHECK(c->err, hipStreamSynchronize(pick_stream(c, stream)));
   return check_device_err(c);
 }
 
@@ -715,22 +693,22 @@ int slamgpu_download_keypoints(slamgpu_ctx* c, int img, slamgpu_keypoint* kps, u
     const ResMirror m = res_mirror(c);
     const int n = m.nkps[img];
     if (n_out) *n_out = n;
-    if (n > cap) return fail(c, SLAMGPU_ECAP, "need %d keypoints, cap %d", n, cap);
+    if (n > cap) return slot(c).fail(SLAMGPU_ECAP, "need %d keypoints, cap %d", n, cap);
     const size_t o = (size_t)img * c->geom.kp_cap;
     if (kps && n) std::memcpy(kps, m.kps + o, sizeof(KeyPoint) * n);
     if (desc && n) std::memcpy(desc, m.desc + o * 32, 32 * (size_t)n);
     return 0;
   }
   int n = 0;
-  HIPCHECK(c, hipStreamSynchronize(c->stream));
-  HIPCHECK(c, hipMemcpy(&n, c->out.nkps + img, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHECK(c->err, hipStreamSynchronize(c->stream));
+  HIPCHECK(c->err, hipMemcpy(&n, c->out.nkps + img, sizeof(int), hipMemcpyDeviceToHost));
   if (n_out) *n_out = n;
-  if (n > cap) return fail(c, SLAMGPU_ECAP, "need %d keypoints, cap %d", n, cap);
+  if (n > cap) return slot(c).fail(SLAMGPU_ECAP, "need %d keypoints, cap %d", n, cap);
   const int64_t o = (int64_t)img * c->geom.kp_cap;
   if (kps && n)
-    HIPCHECK(c, hipMemcpy(kps, c->out.kps + o, sizeof(KeyPoint) * n, hipMemcpyDeviceToHost));
+    HIPCHECK(c->err, hipMemcpy(kps, c->out.kps + o, sizeof(KeyPoint) * n, hipMemcpyDeviceToHost));
   if (desc && n)
-    HIPCHECK(c, hipMemcpy(desc, c->out.desc + o * 32, 32 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(c->err, hipMemcpy(desc, c->out.desc + o * 32, 32 * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -741,21 +719,21 @@ int slamgpu_download_stereo(slamgpu_ctx* c, int frame, float* u_right, float* de
     const ResMirror m = res_mirror(c);
     const int n = m.nkps[0];
     if (n_out) *n_out = n;
-    if (n > cap) return fail(c, SLAMGPU_ECAP, "need %d entries, cap %d", n, cap);
+    if (n > cap) return slot(c).fail(SLAMGPU_ECAP, "need %d entries, cap %d", n, cap);
     if (u_right && n) std::memcpy(u_right, m.u_right, 4 * (size_t)n);
     if (depth && n) std::memcpy(depth, m.depth, 4 * (size_t)n);
     return 0;
   }
   int n = 0;
-  HIPCHECK(c, hipStreamSynchronize(c->stream));
-  HIPCHECK(c, hipMemcpy(&n, c->out.nkps + 2 * frame, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHECK(c->err, hipStreamSynchronize(c->stream));
+  HIPCHECK(c->err, hipMemcpy(&n, c->out.nkps + 2 * frame, sizeof(int), hipMemcpyDeviceToHost));
   if (n_out) *n_out = n;
-  if (n > cap) return fail(c, SLAMGPU_ECAP, "need %d entries, cap %d", n, cap);
+  if (n > cap) return slot(c).fail(SLAMGPU_ECAP, "need %d entries, cap %d", n, cap);
   const int64_t o = (int64_t)frame * c->geom.kp_cap;
   if (u_right && n)
-    HIPCHECK(c, hipMemcpy(u_right, c->sout.u_right + o, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(c->err, hipMemcpy(u_right, c->sout.u_right + o, 4 * (size_t)n, hipMemcpyDeviceToHost));
   if (depth && n)
-    HIPCHECK(c, hipMemcpy(depth, c->sout.depth + o, 4 * (size_t)n, hipMemcpyDeviceToHost));
+    HIPCHECK(c->err, hipMemcpy(depth, c->sout.depth + o, 4 * (size_t)n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -782,9 +760,9 @@ static int parse_dist(const float* dist, int n, Distortion* d) {
 int slamgpu_set_distortion(slamgpu_ctx* c, const float* dist, int n) {
   if (!c) return SLAMGPU_EINVAL;
   Distortion d;
-  if (parse_dist(dist, n, &d)) return fail(c, SLAMGPU_EINVAL, "DistCoef needs 4 or 5 values");
+  if (parse_dist(dist, n, &d)) return slot(c).fail(SLAMGPU_EINVAL, "DistCoef needs 4 or 5 values");
   if (d.k[0] != 0.0f && !c->kps_un) {
-    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c->err, hipSetDevice(c->device));
     if (int rc = dalloc(c, &c->kps_un, (size_t)c->max_images * c->geom.kp_cap)) return rc;
   }
   c->dist = d;
@@ -835,12 +813,12 @@ int slamgpu_download_undistorted_keypoints(slamgpu_ctx* c, int frame, slamgpu_ke
   if (!c || frame < 0 || frame >= c->n_frames_last) return SLAMGPU_EINVAL;
   if (!c->dist_on) return slamgpu_download_keypoints(c, 2 * frame, kps, nullptr, cap, n_out);
   int n = 0;
-  HIPCHECK(c, hipStreamSynchronize(c->stream));
-  HIPCHECK(c, hipMemcpy(&n, c->out.nkps + 2 * frame, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHECK(c->err, hipStreamSynchronize(c->stream));
+  HIPCHECK(c->err, hipMemcpy(&n, c->out.nkps + 2 * frame, sizeof(int), hipMemcpyDeviceToHost));
   if (n_out) *n_out = n;
-  if (n > cap) return fail(c, SLAMGPU_ECAP, "need %d keypoints, cap %d", n, cap);
+  if (n > cap) return slot(c).fail(SLAMGPU_ECAP, "need %d keypoints, cap %d", n, cap);
   if (kps && n)
-    HIPCHECK(c, hipMemcpy(kps, c->kps_un + (int64_t)2 * frame * c->geom.kp_cap,
+    HIPCHECK(c->err, hipMemcpy(kps, c->kps_un + (int64_t)2 * frame * c->geom.kp_cap,
                           sizeof(KeyPoint) * n, hipMemcpyDeviceToHost));
   return 0;
 }
@@ -853,7 +831,7 @@ size_t slamgpu_frame_record_bytes(const slamgpu_ctx* c) {
 int slamgpu_pack_frame_records_device(slamgpu_ctx* c, int first, int n, void* d_dst,
                                       void* stream) {
   if (!c || !d_dst || n < 0 || first < 0 || first + n > c->n_frames_last)
-    return fail(c, SLAMGPU_EINVAL, "pack_frame_records_device: frames [%d, %d) of %d", first,
+    return slot(c).fail(SLAMGPU_EINVAL, "pack_frame_records_device: frames [%d, %d) of %d", first,
                 first + n, c->n_frames_last);
   if (n == 0) return 0;
   const size_t kc = c->geom.kp_cap, rec = slamgpu_frame_record_bytes(c);
@@ -868,7 +846,7 @@ int slamgpu_pack_frame_records_device(slamgpu_ctx* c, int first, int n, void* d_
       {124 * kc, c->sout.depth + kc * first, 4 * kc},
       {128 * kc, c->out.nkps + 2 * first, 8}};
   for (auto& x : f)
-    HIPCHECK(c, hipMemcpy2DAsync(d + x.dst_off, rec, x.src, x.width, x.width, (size_t)n,
+    HIPCHECK(c->err, hipMemcpy2DAsync(d + x.dst_off, rec, x.src, x.width, x.width, (size_t)n,
                                  hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -877,13 +855,13 @@ int slamgpu_make_vo_queries_device(slamgpu_ctx* c, const slamgpu_f2f_pose* d_pos
                                    slamgpu_f2f_query* d_queries, int* d_q_start, int* d_q_count,
                                    int n_frames, void* stream) {
   if (!c || !c->have_cam || n_frames < 1 || n_frames > c->n_frames_last)
-    return fail(c, SLAMGPU_EINVAL, "make_vo_queries_device: bad arguments");
+    return slot(c).fail(SLAMGPU_EINVAL, "make_vo_queries_device: bad arguments");
   TimerScope ts(c);
   launch_vo_queries(left_views(c), c->sout.depth, c->geom.kp_cap, c->cam,
                     reinterpret_cast<const F2FPose*>(d_poses), blocks, c->geom.kp_cap,
                     reinterpret_cast<F2FQuery*>(d_queries), d_q_start, d_q_count, n_frames,
                     pick_stream(c, stream));
-  HIPCHECK(c, hipGetLastError());
+  HIPCHECK(c->err, hipGetLastError());
   return 0;
 }
 
@@ -895,11 +873,11 @@ int slamgpu_set_extract_fork(slamgpu_ctx* c, int on) {
 
 int slamgpu_timing_start(slamgpu_ctx* c, const char* kernel, int max_launches) {
   if (!c || !kernel || max_launches < 1) return SLAMGPU_EINVAL;
-  HIPCHECK(c, hipSetDevice(c->device));
+  HIPCHECK(c->err, hipSetDevice(c->device));
   KernelTimer& t = c->timer;
   while ((int)t.pool.size() < 2 * max_launches) {
     hipEvent_t e;
-    HIPCHECK(c, hipEventCreate(&e));
+    HIPCHECK(c->err, hipEventCreate(&e));
     t.pool.push_back(e);
   }
   t.target = kernel;
@@ -913,9 +891,9 @@ int slamgpu_timing_start(slamgpu_ctx* c, const char* kernel, int max_launches) {
 int slamgpu_timing_stop(slamgpu_ctx* c, void* stream) {
   if (!c) return SLAMGPU_EINVAL;
   c->timer.on = false;
-  HIPCHECK(c, hipStreamSynchronize(pick_stream(c, stream)));
-  HIPCHECK(c, hipDeviceSynchronize());
-  if (c->timer.overflow) return fail(c, SLAMGPU_ECAP, "timing event pool exhausted");
+  HIPCHECK(c->err, hipStreamSynchronize(pick_stream(c, stream)));
+  HIPCHECK(c->err, hipDeviceSynchronize());
+  if (c->timer.overflow) return slot(c).fail(SLAMGPU_ECAP, "timing event pool exhausted");
   return 0;
 }
 
@@ -926,7 +904,7 @@ int slamgpu_timing_read(slamgpu_ctx* c, const char* kernel, double* total_ms, in
   for (size_t i = 0; i < c->timer.used; i++) {
     if (std::strcmp(kernel, "*") != 0 && std::strcmp(kernel, c->timer.names[i]) != 0) continue;
     float ms = 0;
-    HIPCHECK(c, hipEventElapsedTime(&ms, c->timer.pool[2 * i], c->timer.pool[2 * i + 1]));
+    HIPCHECK(c->err, hipEventElapsedTime(&ms, c->timer.pool[2 * i], c->timer.pool[2 * i + 1]));
     tot += ms;
     n++;
   }
@@ -970,7 +948,7 @@ int slamgpu_search_by_projection_frame_device(slamgpu_ctx* c, const slamgpu_f2f_
                                               void* stream) {
   if (!c || !c->have_cam || n_frames < 1 || n_frames > c->n_frames_last ||
       mp_stride < c->geom.kp_cap)
-    return fail(c, SLAMGPU_EINVAL, "search_by_projection_frame_device: bad arguments");
+    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_frame_device: bad arguments");
   int rc = ensure_match_ws(c, total_queries);
   if (rc) return rc;
   MatchIO io{d_q_start, d_q_count, d_map_point, d_blocked, d_nmatches, mp_stride};
@@ -979,7 +957,7 @@ int slamgpu_search_by_projection_frame_device(slamgpu_ctx* c, const slamgpu_f2f_
                       reinterpret_cast<const F2FQuery*>(d_q),
                       reinterpret_cast<const F2FPose*>(d_poses), n_frames, max_queries, c->gws,
                       c->mws, io, pick_stream(c, stream));
-  HIPCHECK(c, hipGetLastError());
+  HIPCHECK(c->err, hipGetLastError());
   return 0;
 }
 
@@ -991,7 +969,7 @@ int slamgpu_search_by_projection_mps_device(slamgpu_ctx* c, const slamgpu_mps_qu
                                             void* stream) {
   if (!c || !c->have_cam || n_frames < 1 || n_frames > c->n_frames_last ||
       mp_stride < c->geom.kp_cap)
-    return fail(c, SLAMGPU_EINVAL, "search_by_projection_mps_device: bad arguments");
+    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_mps_device: bad arguments");
   int rc = ensure_match_ws(c, total_queries);
   if (rc) return rc;
   MatchIO io{d_q_start, d_q_count, d_map_point, d_blocked, d_nmatches, mp_stride};
@@ -999,7 +977,7 @@ int slamgpu_search_by_projection_mps_device(slamgpu_ctx* c, const slamgpu_mps_qu
   launch_search_mps(left_views(c), c->sout.u_right, c->geom.kp_cap, c->cam, c->gd(),
                     reinterpret_cast<const MpsQuery*>(d_q), nnratio, th, n_frames, max_queries,
                     c->gws, c->mws, io, pick_stream(c, stream));
-  HIPCHECK(c, hipGetLastError());
+  HIPCHECK(c->err, hipGetLastError());
   return 0;
 }
 
@@ -1012,7 +990,7 @@ static int host_search(slamgpu_ctx* c, int frame, const QT* queries, int nq, int
                        const void* extra, bool f2f, float nnratio, int th) {
   if (!c || frame < 0 || frame >= c->n_frames_last || nq < 0 || !map_point || !blocked)
     return SLAMGPU_EINVAL;
-  if (n > c->geom.kp_cap) return fail(c, SLAMGPU_EINVAL, "n > kp capacity");
+  if (n > c->geom.kp_cap) return slot(c).fail(SLAMGPU_EINVAL, "n > kp capacity");
   const size_t need = sizeof(QT) * (size_t)std::max(nq, 1) + extra_bytes + 256;
   if (need > c->qbuf_bytes) {
     int rc = dalloc(c, reinterpret_cast<uint8_t**>(&c->d_qbuf), need);
@@ -1023,18 +1001,18 @@ static int host_search(slamgpu_ctx* c, int frame, const QT* queries, int nq, int
   if (rc) return rc;
   hipStream_t st = c->stream;
   uint8_t* qb = static_cast<uint8_t*>(c->d_qbuf);
-  if (nq) HIPCHECK(c, hipMemcpyAsync(qb, queries, sizeof(QT) * nq, hipMemcpyHostToDevice, st));
+  if (nq) HIPCHECK(c->err, hipMemcpyAsync(qb, queries, sizeof(QT) * nq, hipMemcpyHostToDevice, st));
   uint8_t* eb = qb + (sizeof(QT) * (size_t)std::max(nq, 1) + 255) / 256 * 256;
   if (extra_bytes)
-    HIPCHECK(c, hipMemcpyAsync(eb, extra, extra_bytes, hipMemcpyHostToDevice, st));
+    HIPCHECK(c->err, hipMemcpyAsync(eb, extra, extra_bytes, hipMemcpyHostToDevice, st));
   // frame `frame` only: use a one-frame view shifted to that frame
   int meta[2] = {0, nq};
-  HIPCHECK(c, hipMemcpyAsync(c->d_qmeta, meta, sizeof(meta), hipMemcpyHostToDevice, st));
-  HIPCHECK(c, hipMemsetAsync(c->d_mp, 0xff, sizeof(int32_t) * c->geom.kp_cap, st));
-  HIPCHECK(c, hipMemsetAsync(c->d_blk, 0, c->geom.kp_cap, st));
+  HIPCHECK(c->err, hipMemcpyAsync(c->d_qmeta, meta, sizeof(meta), hipMemcpyHostToDevice, st));
+  HIPCHECK(c->err, hipMemsetAsync(c->d_mp, 0xff, sizeof(int32_t) * c->geom.kp_cap, st));
+  HIPCHECK(c->err, hipMemsetAsync(c->d_blk, 0, c->geom.kp_cap, st));
   if (n) {
-    HIPCHECK(c, hipMemcpyAsync(c->d_mp, map_point, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
-    HIPCHECK(c, hipMemcpyAsync(c->d_blk, blocked, n, hipMemcpyHostToDevice, st));
+    HIPCHECK(c->err, hipMemcpyAsync(c->d_mp, map_point, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+    HIPCHECK(c->err, hipMemcpyAsync(c->d_blk, blocked, n, hipMemcpyHostToDevice, st));
   }
   const int64_t kc = c->geom.kp_cap;
   FrameKps cur{(c->dist_on ? c->kps_un : c->out.kps) + 2 * frame * kc,
@@ -1052,14 +1030,14 @@ static int host_search(slamgpu_ctx* c, int frame, const QT* queries, int nq, int
     launch_search_mps(cur, c->sout.u_right + frame * kc, kc, c->cam, c->gd(),
                       reinterpret_cast<const MpsQuery*>(qb), nnratio, th, 1, nq, gw, c->mws, io,
                       st);
-  HIPCHECK(c, hipGetLastError());
+  HIPCHECK(c->err, hipGetLastError());
   if (n) {
-    HIPCHECK(c, hipMemcpyAsync(map_point, c->d_mp, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    HIPCHECK(c, hipMemcpyAsync(blocked, c->d_blk, n, hipMemcpyDeviceToHost, st));
+    HIPCHECK(c->err, hipMemcpyAsync(map_point, c->d_mp, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    HIPCHECK(c->err, hipMemcpyAsync(blocked, c->d_blk, n, hipMemcpyDeviceToHost, st));
   }
   int nm = 0;
-  HIPCHECK(c, hipMemcpyAsync(&nm, c->d_nm, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHECK(c, hipStreamSynchronize(st));
+  HIPCHECK(c->err, hipMemcpyAsync(&nm, c->d_nm, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHECK(c->err, hipStreamSynchronize(st));
   if (nmatches) *nmatches = nm;
   return check_device_err(c);
 }
