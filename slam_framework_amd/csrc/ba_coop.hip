@@ -26,6 +26,7 @@
 
 #include "ba_coop.h"
 #include "ba_device.h"
+#include "ba_ldlt.h"
 #include "timing.h"
 
 namespace slamgpu {
@@ -36,9 +37,6 @@ using namespace ba;
 constexpr int kT = kCoopThreads, kW = kT / 64;
 constexpr int kMaxGrid = 256;  // work-groups of a cooperative launch (<= one per CU)
 constexpr uint32_t kPadKey = 0xFFFFFFFFu;
-#ifndef FS_PROF
-#define FS_PROF 0
-#endif
 constexpr int kChunk = 64;  // S-block pairs per assembly task (one per lane)
 constexpr int kCP = 42;     // per-chunk partials: 36 of the 6x6 block + 6 of the reduced rhs
 
@@ -86,8 +84,6 @@ __device__ __forceinline__ void decode_key(uint32_t key, int& kh, int& kl) {
 // never times out; ~2^22 sleeps (~2 s) without either raise CTL_ERR with the arrivals seen
 // (CTL_ARRIVED of CTL_GRID: work-groups that never became resident). Later barriers do not wait
 // once it is set.
-__device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 __device__ void grid_sync(const CoopWs& w, const int32_t* stop_flag, bool poll) {
   vm_drain();  // this wave's stores have reached L2
   __syncthreads();
@@ -613,60 +609,15 @@ __device__ __forceinline__ void factor_solve(CoopShared& sh, const CoopWs& w, in
 #pragma clang fp contract(fast)  // tolerance-compared FP64 path
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, n = 6 * K;
   if (tid == 0) sh.ok = 1;
-#if FS_PROF  // diagnostic build: thread 0's split of the factorisation into prof[8..13]
-  uint64_t fs_t = __builtin_amdgcn_s_memrealtime();
-  auto fs_tick = [&](int slot) {
-    if (w.prof && tid == 0) {
-      const uint64_t t = __builtin_amdgcn_s_memrealtime();
-      w.prof[slot] += 0.01 * (double)(t - fs_t);
-      fs_t = t;
-    }
-  };
-  if (w.prof && tid == 0) w.prof[13] += 1.0;
-#else
-  auto fs_tick = [](int) {};
-#endif
+  // diagnostic build: thread 0's split of the factorisation into prof[8..13] (tick(k): prof[8 + k])
+  const bool fp = FS_PROF && w.prof && tid == 0;
+  PhaseTimer fs(fp ? w.prof + 8 : nullptr);
+  if (fp) w.prof[13] += 1.0;
+  const DenseRows rows;
   // the diagonal block J by one lane (lane 0 of wave 0): its 21 entries and 6 rhs values in
   // registers, no cross-lane traffic on the pivot chain
   auto diag_factor = [&](int J) {
-    if (lane != 0) return;
-    const int j0 = 6 * J;
-    double A[21], y[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-      y[r] = rhs[j0 + r];
-#pragma unroll
-      for (int k = 0; k <= r; k++) A[r * (r + 1) / 2 + k] = Lp[tri(j0 + r) + j0 + k];
-    }
-    bool good = true;
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-      const double d = A[c * (c + 3) / 2];
-      good = good && d != 0.0;
-      const double rd = d != 0.0 ? 1.0 / d : 0.0;
-      idg[j0 + c] = rd;
-      double l[6];
-#pragma unroll
-      for (int r = c + 1; r < 6; r++) {
-        l[r] = A[r * (r + 1) / 2 + c] * rd;
-        y[r] -= l[r] * y[c];
-        A[r * (r + 1) / 2 + c] = l[r];
-      }
-#pragma unroll
-      for (int r = c + 1; r < 6; r++) {
-        const double ld = l[r] * d;
-#pragma unroll
-        for (int k = c + 1; k <= r; k++) A[r * (r + 1) / 2 + k] -= ld * l[k];
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-#pragma unroll
-      for (int k = 0; k < r; k++) Lp[tri(j0 + r) + j0 + k] = A[r * (r + 1) / 2 + k];
-      dg[j0 + r] = A[r * (r + 3) / 2];
-      rhs[j0 + r] = y[r];
-    }
-    if (!good) sh.ok = 0;
+    if (lane == 0 && !factor_diag_block(Lp, rows, rhs, dg, idg, 6 * J)) sh.ok = 0;
   };
   __syncthreads();
   if (wid == 0) diag_factor(0);
@@ -680,47 +631,35 @@ __device__ __forceinline__ void factor_solve(CoopShared& sh, const CoopWs& w, in
     if (!sh.ok) return;
     {  // panel rows below the diagonal block
       double Ljj[15], rdg[6], yj[6];
-      int q = 0;
-#pragma unroll
-      for (int c = 1; c < 6; c++)
-#pragma unroll
-        for (int k = 0; k < c; k++) Ljj[q++] = Lp[tri(j0 + c) + j0 + k];
+      load_strict_lower(Lp, rows, j0, Ljj);
 #pragma unroll
       for (int c = 0; c < 6; c++) {
         rdg[c] = idg[j0 + c];
         yj[c] = rhs[j0 + c];
       }
       for (int i = j0 + 6 + tid; i < n; i += kT) {
-        const int ro = tri(i) + j0;
-        double v[6];
-        q = 0;
+        const int ro = rows.off(i) + j0;
+        double a[6], v[6], l[6];
 #pragma unroll
-        for (int c = 0; c < 6; c++) {
-          double s = Lp[ro + c];
-#pragma unroll
-          for (int k = 0; k < c; k++) s -= v[k] * Ljj[q++];
-          v[c] = s;
-        }
+        for (int c = 0; c < 6; c++) a[c] = Lp[ro + c];
         double r = rhs[i];
+        panel_row(a, Ljj, rdg, yj, v, l, r);
 #pragma unroll
         for (int c = 0; c < 6; c++) {
           V[(size_t)i * 6 + c] = v[c];
-          const double l = v[c] * rdg[c];
-          Lp[ro + c] = l;
-          r -= l * yj[c];
+          Lp[ro + c] = l[c];
         }
         rhs[i] = r;
       }
     }
-    fs_tick(8);
+    fs.tick(0);
     __syncthreads();
-    fs_tick(9);
+    fs.tick(1);
     if (wid == 0) {
       if (J + 1 < K) {  // block J + 1's lower triangle (21 entries, a lane each), then factor it
         if (lane < 21) {
-          int r = 0;
-          while ((r + 1) * (r + 2) / 2 <= lane) r++;
-          const int c = lane - r * (r + 1) / 2;
+          int r, c;
+          tri_rc(lane, r, c);
           const int i = j0 + 6 + r, k = j0 + 6 + c;
           const int ro = tri(i);
           double s = Lp[ro + k];
@@ -728,9 +667,7 @@ __device__ __forceinline__ void factor_solve(CoopShared& sh, const CoopWs& w, in
           for (int m = 0; m < 6; m++) s -= Lp[ro + j0 + m] * V[(size_t)k * 6 + m];
           Lp[ro + k] = s;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        wave_sync();
         diag_factor(J + 1);
       }
     } else {
@@ -764,34 +701,26 @@ __device__ __forceinline__ void factor_solve(CoopShared& sh, const CoopWs& w, in
         }
       }
     }
-    fs_tick(10);
+    fs.tick(2);
     if (tid == 0)  // heartbeat for the work-groups waiting at the next grid barrier
       __hip_atomic_fetch_add(&w.ctl[CTL_BEAT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    fs_tick(11);
+    fs.tick(3);
   }
   if (wid == 0) {  // z = D^-1 y; L^T x = z from the last 6x6 block up
     for (int i = lane; i < n; i += 64) rhs[i] /= dg[i];
     for (int J = K - 1; J >= 0; J--) {
       const int j0 = 6 * J;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      wave_sync();
       // within the block, by lane 0 in registers (x_c final when c is reached, descending);
       // the 6 values then go to every lane by v_readlane
       double x[6] = {0, 0, 0, 0, 0, 0};
       if (lane == 0) {
         double Lb[15];
-#pragma unroll
-        for (int c = 1; c < 6; c++)
-#pragma unroll
-          for (int r = 0; r < c; r++) Lb[c * (c - 1) / 2 + r] = Lp[tri(j0 + c) + j0 + r];
+        load_strict_lower(Lp, rows, j0, Lb);
 #pragma unroll
         for (int r = 0; r < 6; r++) x[r] = rhs[j0 + r];
-#pragma unroll
-        for (int c = 5; c >= 0; c--)
-#pragma unroll
-          for (int r = 0; r < c; r++) x[r] -= Lb[c * (c - 1) / 2 + r] * x[c];
+        block_back6(Lb, x);
 #pragma unroll
         for (int r = 0; r < 6; r++) rhs[j0 + r] = x[r];
       }
@@ -804,222 +733,11 @@ __device__ __forceinline__ void factor_solve(CoopShared& sh, const CoopWs& w, in
         rhs[i] = sx;
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    wave_sync();
     for (int i = lane; i < n; i += 64) w.xp[i] = rhs[i];
   }
   __syncthreads();
-  fs_tick(12);
-}
-
-__device__ void profile_back_solve(CoopShared& sh, const CoopWs& w, int K, double* Lp,
-                                   double* rhs, const double* dg);
-
-// Work-group barrier ordering LDS only (no vmcnt drain of pending global loads or stores).
-__device__ __forceinline__ void lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-
-// The same LDLT for 6K > kCoopLdsN on the block-profile storage (w.prow / w.pfirst): row i holds
-// columns 6 pfirst[i / 6] .. i, and every fill-in stays inside that envelope, so block column J
-// only touches the active block rows A_J = {I > J : pfirst[I] <= J} -- a band of a few dozen
-// keyframes along the trajectory, plus the rows loop closures reach back from. A_J is kept in
-// LDS (unordered: every element is updated by one lane per column, so the results do not depend
-// on the order) and A_{J+1} is collected while column J's trailing update runs. Otherwise as
-// factor_solve: thread-per-row panel with the forward solve fused, wave 0 updating and factoring
-// the next diagonal block while the other waves apply the trailing update (A_J x A_J below it),
-// two work-group barriers per block column; then D^-1 and the blocked backward solve by wave 0.
-__device__ void factor_solve_profile(CoopShared& sh, const CoopWs& w, int K, double* Lp,
-                                     double* rhs, double* dg, double* idg, double* V) {
-#pragma clang fp contract(fast)  // tolerance-compared FP64 path
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, n = 6 * K;
-  const int64_t* prow = w.prow;
-  const int32_t* pfirst = w.pfirst;
-  // A_J lists in the (unused here) LDS factor storage: two buffers of K entries + 2 counters
-  int* const lists = reinterpret_cast<int*>(sh.S);
-  int* const cnt = lists + 2 * K;
-  if (tid == 0) {
-    sh.ok = 1;
-    cnt[0] = 0;
-  }
-#if FS_PROF  // diagnostic build: thread 0's split of the factorisation into prof[8..13], active
-             // block rows per column: sum in prof[14], max in prof[15]
-  uint64_t fs_t = __builtin_amdgcn_s_memrealtime();
-  auto fs_tick = [&](int slot) {
-    if (w.prof && tid == 0) {
-      const uint64_t t = __builtin_amdgcn_s_memrealtime();
-      w.prof[slot] += 0.01 * (double)(t - fs_t);
-      fs_t = t;
-    }
-  };
-  if (w.prof && tid == 0) w.prof[13] += 1.0;
-#else
-  auto fs_tick = [](int) {};
-#endif
-  auto diag_factor = [&](int J) {  // as in factor_solve, on the profile rows
-    if (lane != 0) return;
-    const int j0 = 6 * J;
-    double A[21], y[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-      y[r] = rhs[j0 + r];
-#pragma unroll
-      for (int k = 0; k <= r; k++) A[r * (r + 1) / 2 + k] = Lp[prow[j0 + r] + j0 + k];
-    }
-    bool good = true;
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-      const double d = A[c * (c + 3) / 2];
-      good = good && d != 0.0;
-      const double rd = d != 0.0 ? 1.0 / d : 0.0;
-      idg[j0 + c] = rd;
-      double l[6];
-#pragma unroll
-      for (int r = c + 1; r < 6; r++) {
-        l[r] = A[r * (r + 1) / 2 + c] * rd;
-        y[r] -= l[r] * y[c];
-        A[r * (r + 1) / 2 + c] = l[r];
-      }
-#pragma unroll
-      for (int r = c + 1; r < 6; r++) {
-        const double ld = l[r] * d;
-#pragma unroll
-        for (int k = c + 1; k <= r; k++) A[r * (r + 1) / 2 + k] -= ld * l[k];
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-#pragma unroll
-      for (int k = 0; k < r; k++) Lp[prow[j0 + r] + j0 + k] = A[r * (r + 1) / 2 + k];
-      dg[j0 + r] = A[r * (r + 3) / 2];
-      rhs[j0 + r] = y[r];
-    }
-    if (!good) sh.ok = 0;
-  };
-  __syncthreads();
-  for (int I = 1 + tid; I < K; I += kT)  // A_0
-    if (pfirst[I] <= 0) lists[atomicAdd(&cnt[0], 1)] = I;
-  if (wid == 0) diag_factor(0);
-  __syncthreads();
-  for (int J = 0; J < K; J++) {
-    const int j0 = 6 * J;
-    if (!sh.ok) return;
-    const int* act = lists + (J & 1) * K;
-    int* nxt = lists + ((J + 1) & 1) * K;
-    const int na = cnt[J & 1], nr = 6 * na;
-#if FS_PROF
-    if (w.prof && tid == 0) {
-      w.prof[14] += (double)na;
-      w.prof[15] = fmax(w.prof[15], (double)na);
-    }
-#endif
-    {  // panel rows of the active blocks (forward solve fused)
-      double Ljj[15], rdg[6], yj[6];
-      int q = 0;
-#pragma unroll
-      for (int c = 1; c < 6; c++)
-#pragma unroll
-        for (int k = 0; k < c; k++) Ljj[q++] = Lp[prow[j0 + c] + j0 + k];
-#pragma unroll
-      for (int c = 0; c < 6; c++) {
-        rdg[c] = idg[j0 + c];
-        yj[c] = rhs[j0 + c];
-      }
-      for (int t = tid; t < nr; t += kT) {
-        const int i = 6 * act[t / 6] + t % 6;
-        const int64_t ro = prow[i] + j0;
-        double v[6];
-        q = 0;
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          double sv = Lp[ro + c];
-#pragma unroll
-          for (int k = 0; k < c; k++) sv -= v[k] * Ljj[q++];
-          v[c] = sv;
-        }
-        double r = rhs[i];
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          V[(size_t)i * 6 + c] = v[c];
-          const double l = v[c] * rdg[c];
-          Lp[ro + c] = l;
-          r -= l * yj[c];
-        }
-        rhs[i] = r;
-      }
-    }
-    fs_tick(8);
-    if (tid == 0) cnt[(J + 1) & 1] = 0;
-    __syncthreads();
-    fs_tick(9);
-    const bool next_active = J + 1 < K && pfirst[J + 1] <= J;
-    if (wid == 0) {
-      if (J + 1 < K) {  // block J + 1: its update by column J (when it is active), then its LDLT
-        if (next_active && lane < 21) {
-          int r = 0;
-          while ((r + 1) * (r + 2) / 2 <= lane) r++;
-          const int c = lane - r * (r + 1) / 2;
-          const int i = j0 + 6 + r, k = j0 + 6 + c;
-          const int64_t ro = prow[i];
-          double sv = Lp[ro + k];
-#pragma unroll
-          for (int m = 0; m < 6; m++) sv -= Lp[ro + j0 + m] * V[(size_t)k * 6 + m];
-          Lp[ro + k] = sv;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        diag_factor(J + 1);
-      }
-    } else {
-      // trailing update A(i, k) -= L(i, J) V(k)^T over the active rows i outside block J + 1 and
-      // the active columns k <= i: a wave per group of 4 rows, lanes over the columns
-      constexpr int kTW = kW - 1;
-      for (int t0 = wid - 1; t0 < nr; t0 += 4 * kTW) {
-        int ic[4];
-        int64_t ro[4];
-        double l[4][6];
-        bool live[4];
-#pragma unroll
-        for (int a = 0; a < 4; a++) {
-          const int t = t0 + a * kTW;
-          const int tt = t < nr ? t : nr - 1;
-          ic[a] = 6 * act[tt / 6] + tt % 6;
-          live[a] = t < nr && ic[a] >= j0 + 12;  // block J + 1 is wave 0's
-          ro[a] = prow[ic[a]];
-#pragma unroll
-          for (int c = 0; c < 6; c++) l[a][c] = Lp[ro[a] + j0 + c];
-        }
-        if (!(live[0] || live[1] || live[2] || live[3])) continue;
-        for (int m = lane; m < nr; m += 64) {
-          const int k = 6 * act[m / 6] + m % 6;
-          double v[6];
-#pragma unroll
-          for (int c = 0; c < 6; c++) v[c] = V[(size_t)k * 6 + c];
-#pragma unroll
-          for (int a = 0; a < 4; a++) {
-            if (!live[a] || k > ic[a]) continue;
-            double sv = Lp[ro[a] + k];
-#pragma unroll
-            for (int c = 0; c < 6; c++) sv -= l[a][c] * v[c];
-            Lp[ro[a] + k] = sv;
-          }
-        }
-      }
-    }
-    fs_tick(10);
-    for (int I = J + 2 + tid; I < K; I += kT)  // A_{J+1}
-      if (pfirst[I] <= J + 1) nxt[atomicAdd(&cnt[(J + 1) & 1], 1)] = I;
-    if (tid == 0)  // heartbeat for the work-groups waiting at the next grid barrier
-      __hip_atomic_fetch_add(&w.ctl[CTL_BEAT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    fs_tick(11);
-  }
-  profile_back_solve(sh, w, K, Lp, rhs, dg);
-  fs_tick(12);
+  fs.tick(4);
 }
 
 // z = D^-1 y; L^T x = z from the last 6x6 block up: lane 0 solves the block (x to LDS), then the
@@ -1031,6 +749,7 @@ __device__ void profile_back_solve(CoopShared& sh, const CoopWs& w, int K, doubl
   const int tid = threadIdx.x, n = 6 * K;
   const int64_t* prow = w.prow;
   const int32_t* pfirst = w.pfirst;
+  const ProfileRows rows{prow};
   double* const xs = sh.rhs;  // 6 doubles (sh.rhs is unused on the profile path)
   // z in LDS when it fits (the unused dense factor storage): the block steps then hand off
   // through LDS only, and the next block's L values are loaded while this block is solved
@@ -1040,12 +759,7 @@ __device__ void profile_back_solve(CoopShared& sh, const CoopWs& w, int K, doubl
     double Lb[15], Lr[6];  // thread 0: block J's strict lower L; every thread: its first row
     auto fetch = [&](int J) {
       const int j0 = 6 * J;
-      if (tid == 0) {
-#pragma unroll
-        for (int c = 1; c < 6; c++)
-#pragma unroll
-          for (int r = 0; r < c; r++) Lb[c * (c - 1) / 2 + r] = Lp[prow[j0 + c] + j0 + r];
-      }
+      if (tid == 0) load_strict_lower(Lp, rows, j0, Lb);
       const int i = 6 * pfirst[J] + tid;
       if (i < j0)
 #pragma unroll
@@ -1065,10 +779,7 @@ __device__ void profile_back_solve(CoopShared& sh, const CoopWs& w, int K, doubl
         double x[6];
 #pragma unroll
         for (int r = 0; r < 6; r++) x[r] = z[j0 + r];
-#pragma unroll
-        for (int c = 5; c >= 0; c--)
-#pragma unroll
-          for (int r = 0; r < c; r++) x[r] -= Lbc[c * (c - 1) / 2 + r] * x[c];
+        block_back6(Lbc, x);
 #pragma unroll
         for (int r = 0; r < 6; r++) {
           z[j0 + r] = x[r];
@@ -1109,16 +820,10 @@ __device__ void profile_back_solve(CoopShared& sh, const CoopWs& w, int K, doubl
     const int j0 = 6 * J;
     if (tid == 0) {
       double Lb[15], x[6];
-#pragma unroll
-      for (int c = 1; c < 6; c++)
-#pragma unroll
-        for (int r = 0; r < c; r++) Lb[c * (c - 1) / 2 + r] = Lp[prow[j0 + c] + j0 + r];
+      load_strict_lower(Lp, rows, j0, Lb);
 #pragma unroll
       for (int r = 0; r < 6; r++) x[r] = rhs[j0 + r];
-#pragma unroll
-      for (int c = 5; c >= 0; c--)
-#pragma unroll
-        for (int r = 0; r < c; r++) x[r] -= Lb[c * (c - 1) / 2 + r] * x[c];
+      block_back6(Lb, x);
 #pragma unroll
       for (int r = 0; r < 6; r++) {
         rhs[j0 + r] = x[r];
@@ -1145,6 +850,144 @@ __device__ void profile_back_solve(CoopShared& sh, const CoopWs& w, int K, doubl
   __syncthreads();
 }
 
+// The same LDLT for 6K > kCoopLdsN on the block-profile storage (w.prow / w.pfirst): row i holds
+// columns 6 pfirst[i / 6] .. i, and every fill-in stays inside that envelope, so block column J
+// only touches the active block rows A_J = {I > J : pfirst[I] <= J} -- a band of a few dozen
+// keyframes along the trajectory, plus the rows loop closures reach back from. A_J is kept in
+// LDS (unordered: every element is updated by one lane per column, so the results do not depend
+// on the order) and A_{J+1} is collected while column J's trailing update runs. Otherwise as
+// factor_solve: thread-per-row panel with the forward solve fused, wave 0 updating and factoring
+// the next diagonal block while the other waves apply the trailing update (A_J x A_J below it),
+// two work-group barriers per block column; then D^-1 and the blocked backward solve by wave 0.
+__device__ void factor_solve_profile(CoopShared& sh, const CoopWs& w, int K, double* Lp,
+                                     double* rhs, double* dg, double* idg, double* V) {
+#pragma clang fp contract(fast)  // tolerance-compared FP64 path
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, n = 6 * K;
+  const int64_t* prow = w.prow;
+  const int32_t* pfirst = w.pfirst;
+  // A_J lists in the (unused here) LDS factor storage: two buffers of K entries + 2 counters
+  int* const lists = reinterpret_cast<int*>(sh.S);
+  int* const cnt = lists + 2 * K;
+  if (tid == 0) {
+    sh.ok = 1;
+    cnt[0] = 0;
+  }
+  // diagnostic build: thread 0's split of the factorisation into prof[8..13], active block rows
+  // per column: sum in prof[14], max in prof[15]
+  const bool fp = FS_PROF && w.prof && tid == 0;
+  PhaseTimer fs(fp ? w.prof + 8 : nullptr);
+  if (fp) w.prof[13] += 1.0;
+  const ProfileRows rows{prow};
+  auto diag_factor = [&](int J) {  // by lane 0 of wave 0, as in factor_solve
+    if (lane == 0 && !factor_diag_block(Lp, rows, rhs, dg, idg, 6 * J)) sh.ok = 0;
+  };
+  __syncthreads();
+  for (int I = 1 + tid; I < K; I += kT)  // A_0
+    if (pfirst[I] <= 0) lists[atomicAdd(&cnt[0], 1)] = I;
+  if (wid == 0) diag_factor(0);
+  __syncthreads();
+  for (int J = 0; J < K; J++) {
+    const int j0 = 6 * J;
+    if (!sh.ok) return;
+    const int* act = lists + (J & 1) * K;
+    int* nxt = lists + ((J + 1) & 1) * K;
+    const int na = cnt[J & 1], nr = 6 * na;
+    if (fp) {
+      w.prof[14] += (double)na;
+      w.prof[15] = fmax(w.prof[15], (double)na);
+    }
+    {  // panel rows of the active blocks (forward solve fused)
+      double Ljj[15], rdg[6], yj[6];
+      load_strict_lower(Lp, rows, j0, Ljj);
+#pragma unroll
+      for (int c = 0; c < 6; c++) {
+        rdg[c] = idg[j0 + c];
+        yj[c] = rhs[j0 + c];
+      }
+      for (int t = tid; t < nr; t += kT) {
+        const int i = 6 * act[t / 6] + t % 6;
+        const int64_t ro = rows.off(i) + j0;
+        double a[6], v[6], l[6];
+#pragma unroll
+        for (int c = 0; c < 6; c++) a[c] = Lp[ro + c];
+        double r = rhs[i];
+        panel_row(a, Ljj, rdg, yj, v, l, r);
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+          V[(size_t)i * 6 + c] = v[c];
+          Lp[ro + c] = l[c];
+        }
+        rhs[i] = r;
+      }
+    }
+    fs.tick(0);
+    if (tid == 0) cnt[(J + 1) & 1] = 0;
+    __syncthreads();
+    fs.tick(1);
+    const bool next_active = J + 1 < K && pfirst[J + 1] <= J;
+    if (wid == 0) {
+      if (J + 1 < K) {  // block J + 1: its update by column J (when it is active), then its LDLT
+        if (next_active && lane < 21) {
+          int r, c;
+          tri_rc(lane, r, c);
+          const int i = j0 + 6 + r, k = j0 + 6 + c;
+          const int64_t ro = prow[i];
+          double sv = Lp[ro + k];
+#pragma unroll
+          for (int m = 0; m < 6; m++) sv -= Lp[ro + j0 + m] * V[(size_t)k * 6 + m];
+          Lp[ro + k] = sv;
+        }
+        wave_sync();
+        diag_factor(J + 1);
+      }
+    } else {
+      // trailing update A(i, k) -= L(i, J) V(k)^T over the active rows i outside block J + 1 and
+      // the active columns k <= i: a wave per group of 4 rows, lanes over the columns
+      constexpr int kTW = kW - 1;
+      for (int t0 = wid - 1; t0 < nr; t0 += 4 * kTW) {
+        int ic[4];
+        int64_t ro[4];
+        double l[4][6];
+        bool live[4];
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+          const int t = t0 + a * kTW;
+          const int tt = t < nr ? t : nr - 1;
+          ic[a] = 6 * act[tt / 6] + tt % 6;
+          live[a] = t < nr && ic[a] >= j0 + 12;  // block J + 1 is wave 0's
+          ro[a] = prow[ic[a]];
+#pragma unroll
+          for (int c = 0; c < 6; c++) l[a][c] = Lp[ro[a] + j0 + c];
+        }
+        if (!(live[0] || live[1] || live[2] || live[3])) continue;
+        for (int m = lane; m < nr; m += 64) {
+          const int k = 6 * act[m / 6] + m % 6;
+          double v[6];
+#pragma unroll
+          for (int c = 0; c < 6; c++) v[c] = V[(size_t)k * 6 + c];
+#pragma unroll
+          for (int a = 0; a < 4; a++) {
+            if (!live[a] || k > ic[a]) continue;
+            double sv = Lp[ro[a] + k];
+#pragma unroll
+            for (int c = 0; c < 6; c++) sv -= l[a][c] * v[c];
+            Lp[ro[a] + k] = sv;
+          }
+        }
+      }
+    }
+    fs.tick(2);
+    for (int I = J + 2 + tid; I < K; I += kT)  // A_{J+1}
+      if (pfirst[I] <= J + 1) nxt[atomicAdd(&cnt[(J + 1) & 1], 1)] = I;
+    if (tid == 0)  // heartbeat for the work-groups waiting at the next grid barrier
+      __hip_atomic_fetch_add(&w.ctl[CTL_BEAT], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    fs.tick(3);
+  }
+  profile_back_solve(sh, w, K, Lp, rhs, dg);
+  fs.tick(4);
+}
+
 // ---- the profile LDLT over the whole grid (6K > kCoopLdsN) ---------------------------------
 // Block row I of S (its rows of L and rhs) belongs to work-group I % G for the whole
 // factorisation: its panel rows and trailing updates are computed there, so L never crosses
@@ -1159,10 +1002,12 @@ __device__ void profile_back_solve(CoopShared& sh, const CoopWs& w, int K, doubl
 // owner's trailing update and panel, so the replicas equal the owner's values bit for bit -- and
 // then factors block J + 1 itself (one lane); the owner also writes that factor to the profile
 // for the backward solve. Every element sees the same operations in the same order as in
-// factor_solve_profile (identical results). V is double-buffered by column parity: a work-group
-// runs at most one column ahead of the slowest (it cannot pass column J + 1's panel flags before
-// every work-group has finished column J). Active block rows per column <= prof_na_cap(K) (their
-// V rows and replicas fit the LDS; host-computed na_max, else work-group 0 factors alone).
+// factor_solve_profile -- both call ba_ldlt.h's diag_ldlt and panel_row -- so the two give
+// identical results (tests/test_gba_gpu.py compares them bit for bit). V is double-buffered by
+// column parity: a work-group runs at most one column ahead of the slowest (it cannot pass column
+// J + 1's panel flags before every work-group has finished column J). Active block rows per
+// column <= prof_na_cap(K) (their V rows and replicas fit the LDS; host-computed na_max, else
+// work-group 0 factors alone).
 
 // Wave 0: spin until every work-group's flag (pflag[32 g], one 128-byte line each) reaches target.
 // False once the grid has given up (CTL_ERR), or when no flag moved for ~2^22 sleeps (raised here).
@@ -1225,36 +1070,6 @@ __device__ __forceinline__ int prof_na_cap(int K) {
   return cap > 0 ? cap : 0;
 }
 
-// The 6x6 LDLT of a diagonal block (lower triangle A, 21 doubles row-major packed) with the
-// forward solve of its rhs slice y: strict lower L (15, by column c then row r < c, the order the
-// panel reads it), D^-1, D and the solved y in place. False on an exact zero pivot. Same
-// statements as factor_solve_profile's diag_factor.
-__device__ bool diag_ldlt(double (&A)[21], double (&y)[6], double (&rdg)[6]) {
-#pragma clang fp contract(fast)  // tolerance-compared FP64 path
-  bool good = true;
-#pragma unroll
-  for (int c = 0; c < 6; c++) {
-    const double d = A[c * (c + 3) / 2];
-    good = good && d != 0.0;
-    const double rd = d != 0.0 ? 1.0 / d : 0.0;
-    rdg[c] = rd;
-    double l[6];
-#pragma unroll
-    for (int r = c + 1; r < 6; r++) {
-      l[r] = A[r * (r + 1) / 2 + c] * rd;
-      y[r] -= l[r] * y[c];
-      A[r * (r + 1) / 2 + c] = l[r];
-    }
-#pragma unroll
-    for (int r = c + 1; r < 6; r++) {
-      const double ld = l[r] * d;
-#pragma unroll
-      for (int k = c + 1; k <= r; k++) A[r * (r + 1) / 2 + k] -= ld * l[k];
-    }
-  }
-  return good;
-}
-
 // Every work-group. Returns false (work-group-uniform, the same in every work-group) on a zero
 // pivot or when the grid gave up; the panel flags must be 0 on entry (zeroed before the grid
 // barrier that precedes it).
@@ -1266,6 +1081,7 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
   const int G = gridDim.x, wg = blockIdx.x;
   const int64_t* prow = w.prow;
   const int32_t* pfirst = w.pfirst;
+  const ProfileRows rows{prow};
   const int cap = prof_na_cap(K);
   int* const lists = reinterpret_cast<int*>(sh.S);
   int* const cnt = lists + 2 * K;  // [0], [1]: list sizes; [2]: own count; [3]: flags seen;
@@ -1290,9 +1106,8 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
     const int i0 = 6 * I;
     const bool act_kf = kf_active(w, I);
     if (e >= 21) return act_kf ? w.bs[i0 + e - 21] : 0.0;
-    int r = 0;
-    while ((r + 1) * (r + 2) / 2 <= e) r++;
-    const int c = e - r * (r + 1) / 2;
+    int r, c;
+    tri_rc(e, r, c);
     return (!act_kf && c == r) ? 1.0 : w.S[prow[i0 + r] + i0 + c];
   };
   // a block entering the active set takes a free slot (filled by initial())
@@ -1307,11 +1122,10 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
 #pragma unroll
     for (int r = 0; r < 6; r++) y[r] = src[21 + r];
     const bool good = diag_ldlt(A, y, rdg);
-    int q = 0;
+    double Ljj[15];
+    load_strict_lower(A, DenseRows{}, 0, Ljj);  // the packed block is a dense factor of 6 rows
 #pragma unroll
-    for (int c = 1; c < 6; c++)
-#pragma unroll
-      for (int k = 0; k < c; k++) pd[q++] = A[c * (c + 1) / 2 + k];
+    for (int q = 0; q < 15; q++) pd[q] = Ljj[q];
 #pragma unroll
     for (int c = 0; c < 6; c++) {
       pd[15 + c] = rdg[c];
@@ -1319,6 +1133,8 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
     }
     pd[27] = good ? 1.0 : 0.0;
     if (J % G == wg) {
+      // factor_diag_block's store, written out: as a shared helper it cost the 1500-keyframe
+      // global BA 0.6 % (the same instructions here, another register allocation elsewhere)
       const int j0 = 6 * J;
 #pragma unroll
       for (int r = 0; r < 6; r++) {
@@ -1351,20 +1167,11 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
   if (tid < kRep && K > 0) nx[tid] = initial(0, tid);  // block 0: no update before column 0
   __syncthreads();
   bool ok = true;
-#if FS_PROF  // diagnostic build: thread 0 of work-group 0 splits each column into prof[8..12]
-  const bool gp = w.prof && wg == 0 && tid == 0;
-  uint64_t gt = __builtin_amdgcn_s_memrealtime();
+  // diagnostic build: thread 0 of work-group 0 splits each column into prof[8..12], summed here
+  // and written once at the end
+  const bool gp = FS_PROF && w.prof && wg == 0 && tid == 0;
   double gacc[5] = {0, 0, 0, 0, 0};
-  auto gtick = [&](int slot) {
-    if (gp) {
-      const uint64_t t = __builtin_amdgcn_s_memrealtime();
-      gacc[slot] += 0.01 * (double)(t - gt);
-      gt = t;
-    }
-  };
-#else
-  auto gtick = [](int) {};
-#endif
+  PhaseTimer gt(gp ? gacc : nullptr);
   for (int J = 0; J < K; J++) {
     const int j0 = 6 * J;
     const int* act = lists + (J & 1) * K;
@@ -1393,7 +1200,7 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
       if (act[t] % G == wg) own[atomicAdd(&cnt[2], 1)] = t;
     __syncthreads();
     const int nro = 6 * cnt[2];
-    gtick(0);
+    gt.tick(0);
     // ---- panel rows of the own active blocks (forward solve fused); V published, L_iJ kept
     {
       double Ljj[15], rdg[6], yj[6];
@@ -1406,26 +1213,19 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
       }
       for (int t = tid; t < nro; t += kT) {
         const int i = 6 * act[own[t / 6]] + t % 6;
-        const int64_t pr = prow[i];
+        const int64_t pr = rows.off(i);
         sro[t] = (int)pr;
         const int64_t ro = pr + j0;
-        double v[6];
-        int q = 0;
+        double a[6], v[6], l[6];
 #pragma unroll
-        for (int c = 0; c < 6; c++) {
-          double sv = Lp[ro + c];
-#pragma unroll
-          for (int k = 0; k < c; k++) sv -= v[k] * Ljj[q++];
-          v[c] = sv;
-        }
+        for (int c = 0; c < 6; c++) a[c] = Lp[ro + c];
         double r = rhs[i];
+        panel_row(a, Ljj, rdg, yj, v, l, r);
 #pragma unroll
         for (int c = 0; c < 6; c++) {
           st_wt(Vp + (size_t)i * 6 + c, v[c]);
-          const double l = v[c] * rdg[c];
-          Lp[ro + c] = l;
-          sL[t * 6 + c] = l;
-          r -= l * yj[c];
+          Lp[ro + c] = l[c];
+          sL[t * 6 + c] = l[c];
         }
         rhs[i] = r;
       }
@@ -1458,7 +1258,7 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
       }
       if (wid == 1 && J + 1 < K && spf[J + 1] > J && lane < kRep) nx[lane] = initial(J + 1, lane);
     }
-    gtick(1);
+    gt.tick(1);
     // ---- every panel of column J: the active V rows to LDS
     if (wid == 0) {
       const bool got = wait_flags(w, pflag, J + 1);
@@ -1469,7 +1269,7 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
       ok = false;
       break;
     }
-    gtick(2);
+    gt.tick(2);
     for (int q = tid; q < 36 * na; q += kT) {
       const int t = q / 6, c = q - 6 * t;
       sV[q] = ld_wt(Vp + (size_t)(6 * act[t / 6] + t % 6) * 6 + c);
@@ -1498,9 +1298,8 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
         const int t = q / kRep, e = q - kRep * t;
         double* R = rep + (size_t)slot_of[act[t]] * kRep;
         if (e < 21) {  // diagonal entry (r, c): -= L(row r) V(row c)^T
-          int r = 0;
-          while ((r + 1) * (r + 2) / 2 <= e) r++;
-          const int c = e - r * (r + 1) / 2;
+          int r, c;
+          tri_rc(e, r, c);
           const double* vr = sV + (6 * t + r) * 6;
           const double* vc = sV + (6 * t + c) * 6;
           double sv = R[e];
@@ -1520,7 +1319,7 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
       }
     }
     __syncthreads();
-    gtick(3);
+    gt.tick(3);
     // ---- A_{J+1} = A_J without block J + 1, and the entering blocks (block J + 1 is factored at
     // the start of the next column)
     if (J + 1 < K) {
@@ -1531,14 +1330,12 @@ __device__ bool factor_profile_grid(CoopShared& sh, const CoopWs& w, int K, doub
       }
     }
     __syncthreads();
-    gtick(4);
+    gt.tick(4);
   }
-#if FS_PROF
   if (gp) {
     for (int k = 0; k < 5; k++) w.prof[8 + k] += gacc[k];
     w.prof[13] -= 1.0;  // negative: the grid factorisation's split
   }
-#endif
   vm_drain();
   __syncthreads();
   return ok;
@@ -1663,12 +1460,12 @@ __global__ __launch_bounds__(kT) void ba_coop_kernel(PoseParams P, CoopProblem p
   int32_t* const Gflag = reinterpret_cast<int32_t*>(Gv2 + (size_t)6 * n + 64);
   // the profile LDLT over the whole grid when the active V rows fit the LDS (host: na_max)
   const bool grid_factor = !in_lds && w.mwg && gridDim.x > 1 && w.na_max <= prof_na_cap(K);
-  // optional per-phase wall clock of work-group 0 (s_memrealtime: 100 MHz)
+  // optional per-phase wall clock of work-group 0 (phase_clock: 100 MHz)
   if (tid < 8) sh.pacc[tid] = 0.0;
-  if (tid == 0) sh.pt0 = __builtin_amdgcn_s_memrealtime();
+  if (tid == 0) sh.pt0 = phase_clock();
   auto tick = [&](int slot) {  // thread 0 of work-group 0 only: no registers held across phases
     if (w.prof && wg == 0 && tid == 0) {
-      const uint64_t t = __builtin_amdgcn_s_memrealtime();
+      const uint64_t t = phase_clock();
       sh.pacc[slot] += 0.01 * (double)(t - sh.pt0);
       sh.pt0 = t;
     }

@@ -61,6 +61,21 @@ def test_global_ba_both_profile_factorisations(oracle, gpu_lib, monkeypatch, mwg
     assert_close(pts, pts_o, P["points"], "points")
 
 
+def test_global_ba_profile_factorisations_equal_bit_for_bit(gpu_lib, monkeypatch):
+    """factor_profile_grid and factor_solve_profile apply the same operations in the same order
+    to every element (both are built from csrc/ba_ldlt.h's pieces), so the two runs agree bit for
+    bit. 26 keyframes: the smallest window past the LDS solver, where both profile solvers run."""
+    P = gba_problem(38, 26, 3000, spacing=0.8, outlier_frac=0.02)
+    res = {}
+    for mwg in ("1", "0"):
+        monkeypatch.setenv("SLAMGPU_GBA_MWG", mwg)
+        monkeypatch.setenv("SLAMGPU_GBA_MWG_MIN_KF", "0")
+        res[mwg] = run(gpu_lib, P, 10, True)
+    assert res["1"][2] == res["0"][2]
+    assert np.array_equal(res["1"][0], res["0"][0]), "keyframe poses"
+    assert np.array_equal(res["1"][1], res["0"][1]), "points"
+
+
 def test_global_ba_unobserved_point_kept(oracle, gpu_lib):
     """A point without observations is not optimised (optimizer.cpp:149-152)."""
     P = gba_problem(35, 8, 400)
