@@ -13,8 +13,12 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -25,6 +29,7 @@
 #include "slamgpu_kfmatch.h"
 #include "slamgpu_loopmatch.h"
 #include "slamgpu_optimizer.h"
+#include "slamgpu_sim3solver.h"
 
 namespace slamgpu_adapter {
 
@@ -926,6 +931,204 @@ inline int optimize_sim3(int kf1_index, int kf2_index, const KeyFrameView* kfs,
     if (!inl[c]) matches1[p.match_index[c]] = -1;
   return n_in;
 }
+
+// ---- Sim3Solver (src/solvers/sim3solver.h, sim3solver.cpp), LoopCloser::ComputeSim3
+// (loop_closer.cpp:336-376) ---------------------------------------------------------------------
+// The effective mRansacMaxIts of SetRansacParameters (:127-137), host libm as the reference: float
+// epsilon, std::pow(float, int) and std::log in double, N == minInliers -> 1. A quotient that is
+// no positive int (epsilon >= 1, or 0) is what the reference's x86 build converts to INT_MIN.
+inline int sim3_ransac_iterations(int N, double probability, int minInliers, int maxIterations) {
+  const float epsilon = (float)minInliers / N;
+  int nIterations;
+  if (minInliers == N) {
+    nIterations = 1;
+  } else {
+    const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3)));
+    nIterations = v >= 1.0 && v <= 2147483647.0 ? (int)v : INT_MIN;
+  }
+  return std::max(1, std::min(nIterations, maxIterations));
+}
+
+// DUtils::Random::RandomInt (DUtils/Random.cpp:47-50) on the C library's rand().
+inline int reference_random_int(int min, int max) {
+  const int d = max - min + 1;
+  return int(((double)std::rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+}
+
+// The reference class's surface over the views. The constructor does the gather of :64-105
+// (mvnIndices1 and the skip rules: no map point on either side, a bad one, GetIndexInKeyFrame < 0)
+// and, like the reference's, evaluates nothing. SetRansacParameters draws the WHOLE schedule with
+// the functor -- in the order the reference would consume the draws for this solver alone; several
+// interleaved solvers consume rand() in another global order than the reference's lazy draws,
+// which is why the draws are an input of the C ABI -- and makes the one synchronous call.
+// iterate / find then replay :142-217 from the per-hypothesis counts and the events. The
+// constructor's default parameters (0.99, 6, 300) are evaluated by the first iterate if
+// SetRansacParameters was never called.
+class Sim3SolverCore {
+ public:
+  using RandomInt = std::function<int(int, int)>;
+
+  Sim3SolverCore(int kf1_index, int kf2_index, const KeyFrameView* kfs, const MapPointView* mps,
+                 const int32_t* vpMatched12, int n_matched, const float K1[4], const float K2[4],
+                 const float* sigma2_1, const float* sigma2_2, int nlevels, bool bFixScale,
+                 RandomInt random_int = reference_random_int)
+      : mN1_(n_matched), fix_scale_(bFixScale), nlevels_(nlevels),
+        sigma2_1_(sigma2_1, sigma2_1 + nlevels), sigma2_2_(sigma2_2, sigma2_2 + nlevels),
+        random_int_(std::move(random_int)) {
+    std::memcpy(K1_, K1, sizeof K1_);
+    std::memcpy(K2_, K2, sizeof K2_);
+    const KeyFrameView& kf1 = kfs[kf1_index];
+    const KeyFrameView& kf2 = kfs[kf2_index];
+    auto index_in = [&](int m, int kf) {  // MapPoint::GetIndexInKeyFrame
+      for (int o = 0; o < mps[m].n_obs; ++o)
+        if (mps[m].obs[o].keyframe == kf) return (int)mps[m].obs[o].keypoint;
+      return -1;
+    };
+    for (int i1 = 0; i1 < n_matched; ++i1) {
+      const int m2 = vpMatched12[i1];
+      if (m2 < 0) continue;
+      const int m1 = kf1.map_points[i1];
+      if (m1 < 0) continue;
+      if (mps[m1].bad || mps[m2].bad) continue;
+      const int i_kf1 = index_in(m1, kf1_index), i_kf2 = index_in(m2, kf2_index);
+      if (i_kf1 < 0 || i_kf2 < 0) continue;
+      const slamgpu_keypoint& kp1 = kf1.undist_kps[i_kf1];
+      const slamgpu_keypoint& kp2 = kf2.undist_kps[i_kf2];
+      slamgpu_sim3_match c;
+      for (int r = 0; r < 3; ++r) {
+        c.x1c[r] = cv_gemm_row(kf1.Tcw, r, mps[m1].xyz);
+        c.x2c[r] = cv_gemm_row(kf2.Tcw, r, mps[m2].xyz);
+      }
+      c.u1 = kp1.x, c.v1 = kp1.y, c.u2 = kp2.x, c.v2 = kp2.y;
+      c.octave1 = kp1.octave;
+      c.octave2 = kp2.octave;
+      matches_.push_back(c);
+      indices1_.push_back(i1);
+    }
+  }
+
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    prob_ = probability, min_inliers_ = minInliers, max_its_arg_ = maxIterations;
+    const int N = (int)matches_.size();
+    max_its_ = sim3_ransac_iterations(N, probability, minInliers, maxIterations);
+    iterations_ = 0;
+    evaluated_ = true;
+    draws_.clear();
+    hyp_.clear();
+    bits_.clear();
+    events_.clear();
+    if (N < minInliers) return;  // iterate returns at once (:151-154): nothing is drawn
+    if (N < 3) throw std::runtime_error("slamgpu: Sim3Solver needs 3 correspondences");
+    for (int k = 0; k < max_its_; ++k)
+      for (int i = 0; i < 3; ++i) draws_.push_back(random_int_(0, N - 1 - i));
+    words_ = SLAMGPU_SIM3_MASK_WORDS(N);
+    hyp_.resize(max_its_);
+    bits_.resize((size_t)max_its_ * words_);
+    events_.resize(max_its_);
+    int ne = 0;
+    throw_if(slamgpu_sim3_ransac(K1_, K2_, sigma2_1_.data(), sigma2_2_.data(), nlevels_,
+                                 matches_.data(), N, draws_.data(), max_its_, minInliers,
+                                 fix_scale_ ? 1 : 0, hyp_.data(), bits_.data(), events_.data(),
+                                 &ne),
+             slamgpu_sim3solver_last_error);
+    events_.resize(ne);
+  }
+
+  // iterate (:142-211): the 0-based iteration whose transform the reference returns (T12 below
+  // gives the matrix), or -1 for its empty cv::Mat.
+  int iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+    if (!evaluated_) SetRansacParameters(prob_, min_inliers_, max_its_arg_);
+    bNoMore = false;
+    vbInliers.assign(mN1_, false);
+    nInliers = 0;
+    const int N = (int)matches_.size();
+    if (N < min_inliers_) {
+      bNoMore = true;
+      return -1;
+    }
+    const int start = iterations_;
+    const int end = std::min(max_its_, start + std::max(nIterations, 0));
+    size_t j = 0;
+    while (j < events_.size() && events_[j] < start) ++j;
+    if (j < events_.size() && events_[j] < end) {
+      const int k = events_[j];
+      iterations_ = k + 1;
+      nInliers = hyp_[k].n_inliers;
+      for (int i = 0; i < N; ++i)
+        if (bits_[(size_t)k * words_ + i / 64] >> (i % 64) & 1) vbInliers[indices1_[i]] = true;
+      return k;
+    }
+    iterations_ = end;
+    if (iterations_ >= max_its_) bNoMore = true;
+    return -1;
+  }
+  // find (:213-217)
+  int find(std::vector<bool>& vbInliers12, int& nInliers) {
+    if (!evaluated_) SetRansacParameters(prob_, min_inliers_, max_its_arg_);
+    bool flag;
+    return iterate(max_its_, flag, vbInliers12, nInliers);
+  }
+
+  // mT12i of iteration k, 4x4 row-major: [ms12i * mR12i | mt12i; 0 0 0 1] (:325-330).
+  void T12(int k, float T[16]) const {
+    const slamgpu_sim3_hyp& h = hyp_[k];
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) T[4 * r + c] = h.s12 * h.R12[3 * r + c];
+      T[4 * r + 3] = h.t12[r];
+      T[12 + r] = 0.0f;
+    }
+    T[15] = 1.0f;
+  }
+
+  // mBestRotation / mBestTranslation / mBestScale as the reference leaves them, also after a call
+  // that returned nothing: the last iteration, among those run, that reached the running maximum
+  // (the >= of :186). false while the reference's matrices are still empty.
+  bool GetEstimatedRotation(float R[9]) const {
+    const int k = best();
+    if (k >= 0) std::memcpy(R, hyp_[k].R12, sizeof(float) * 9);
+    return k >= 0;
+  }
+  bool GetEstimatedTranslation(float t[3]) const {
+    const int k = best();
+    if (k >= 0) std::memcpy(t, hyp_[k].t12, sizeof(float) * 3);
+    return k >= 0;
+  }
+  float GetEstimatedScale() const {
+    const int k = best();
+    return k >= 0 ? hyp_[k].s12 : 0.0f;
+  }
+
+  const std::vector<slamgpu_sim3_match>& matches() const { return matches_; }
+  const std::vector<int32_t>& indices1() const { return indices1_; }  // mvnIndices1
+  const std::vector<int32_t>& draws() const { return draws_; }
+  const slamgpu_sim3_hyp& hypothesis(int k) const { return hyp_[k]; }
+  int max_iterations() const { return max_its_; }  // the effective mRansacMaxIts
+
+ private:
+  int best() const {
+    int k = -1, n = 0;
+    for (int i = 0; i < iterations_ && i < (int)hyp_.size(); ++i)
+      if (hyp_[i].n_inliers >= n) n = hyp_[i].n_inliers, k = i;
+    return k;
+  }
+
+  int mN1_;
+  bool fix_scale_;
+  int nlevels_;
+  float K1_[4], K2_[4];
+  std::vector<float> sigma2_1_, sigma2_2_;
+  RandomInt random_int_;
+  std::vector<slamgpu_sim3_match> matches_;
+  std::vector<int32_t> indices1_;
+  double prob_ = 0.99;
+  int min_inliers_ = 6, max_its_arg_ = 300, max_its_ = 300;
+  bool evaluated_ = false;
+  int iterations_ = 0;  // mnIterations
+  int words_ = 0;
+  std::vector<int32_t> draws_, events_;
+  std::vector<slamgpu_sim3_hyp> hyp_;
+  std::vector<uint64_t> bits_;
+};
 
 // ---- Optimizer::BundleAdjustment (optimizer.cpp:33-207), GlobalBundleAdjustemnt (:18-31) ----
 // Vertices: every keyframe that is not bad (fixed when Id() == 0), every map point that is not

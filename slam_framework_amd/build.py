@@ -40,6 +40,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_adapter_check()
         build_geometry_check()
         build_host_stage_check()
+        build_sim3solver_adapter_check()
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -68,6 +69,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_adapter_check()
     build_geometry_check()
     build_host_stage_check()
+    build_sim3solver_adapter_check()
     return LIB
 
 
@@ -108,6 +110,25 @@ def build_adapter_check() -> str:
                     os.path.join(ROOT, "include"), ADAPTER_SRC, "-L", PKG, "-lslamgpu",
                     "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", ADAPTER_BIN], check=True)
     return ADAPTER_BIN
+
+
+SIM3SOLVER_ADAPTER_SRC = os.path.join(ROOT, "tests", "sim3solver_adapter_check.cpp")
+SIM3SOLVER_ADAPTER_BIN = os.path.join(ROOT, "tests", "sim3solver_adapter_check")
+
+
+def build_sim3solver_adapter_check() -> str:
+    """g++ build of tests/sim3solver_adapter_check.cpp: Sim3SolverCore of
+    include/slamgpu_adapters.hpp (the gather, the eager draws, the iterate / find replay) driven
+    from C++ against libslamgpu.so."""
+    deps = [SIM3SOLVER_ADAPTER_SRC, LIB] + glob.glob(os.path.join(ROOT, "include", "*.h*"))
+    if os.path.exists(SIM3SOLVER_ADAPTER_BIN) and os.path.getmtime(SIM3SOLVER_ADAPTER_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return SIM3SOLVER_ADAPTER_BIN
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I",
+                    os.path.join(ROOT, "include"), SIM3SOLVER_ADAPTER_SRC, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", SIM3SOLVER_ADAPTER_BIN],
+                   check=True)
+    return SIM3SOLVER_ADAPTER_BIN
 
 
 GEOMETRY_SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")

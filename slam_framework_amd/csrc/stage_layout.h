@@ -15,6 +15,7 @@
 #include "../../include/slamgpu_bow.h"
 #include "../../include/slamgpu_loopmatch.h"
 #include "../../include/slamgpu_optimizer.h"
+#include "../../include/slamgpu_sim3solver.h"
 #include "host_common.h"
 
 namespace slamgpu {
@@ -143,6 +144,16 @@ inline SearchSim3Layout layout_search_sim3(StageLayout& L, size_t n1, size_t n2)
           L.take<slamgpu_kf>(2), L.take<slamgpu_fuse_point>(n1 + n2),
           L.take<slamgpu_sim3_pair>(1), L.take(stride), L.take(stride), L.take<int32_t>(stride),
           L.take<int32_t>(stride), L.take<int32_t>(stride), L.take<int32_t>(1)};
+}
+
+// The RANSAC Sim3 solver of one candidate: n correspondences, n_its iterations of 3 draws; the
+// mask rows are SLAMGPU_SIM3_MASK_WORDS(n) words each.
+struct Sim3RansacLayout { size_t matches, draws, job, hyp, bits, events, n_events; };
+inline Sim3RansacLayout layout_sim3_ransac(StageLayout& L, size_t n, size_t n_its) {
+  return {L.take<slamgpu_sim3_match>(n), L.take<int32_t>(3 * n_its),
+          L.take<slamgpu_sim3_ransac_job>(1), L.take<slamgpu_sim3_hyp>(n_its),
+          L.take<uint64_t>(n_its * SLAMGPU_SIM3_MASK_WORDS(n)), L.take<int32_t>(n_its),
+          L.take<int32_t>(1)};
 }
 
 // A host FeatureVector (n_nodes > 0) must be well formed before its indices reach the device:

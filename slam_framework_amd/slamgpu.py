@@ -36,6 +36,14 @@ MPS_QUERY_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<
 SIM3_MATCH_DTYPE = np.dtype([("x1c", "<f4", (3,)), ("x2c", "<f4", (3,)), ("u1", "<f4"),
                              ("v1", "<f4"), ("u2", "<f4"), ("v2", "<f4"), ("octave1", "<i4"),
                              ("octave2", "<i4")])
+# slamgpu_sim3_ransac_job / slamgpu_sim3_hyp (include/slamgpu_sim3solver.h): one candidate of the
+# RANSAC Sim3 solver, one hypothesis (mR12i, mt12i, ms12i, mnInliersi) of its schedule.
+SIM3_RANSAC_JOB_DTYPE = np.dtype([("match_begin", "<i4"), ("n", "<i4"), ("draw_begin", "<i4"),
+                                  ("n_its", "<i4"), ("min_inliers", "<i4"), ("fix_scale", "<i4")])
+SIM3_HYP_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4"),
+                           ("n_inliers", "<i4"), ("pad", "<i4", (2,))])
+SIM3_MAX_MATCHES = 4096
+SIM3_RANSAC_MAX_ITS = 300
 # slamgpu_sim3_edge (include/slamgpu_optimizer.h): one EdgeSim3 of the essential graph.
 SIM3_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("pad", "<i4", (2,)), ("Sji", "<f8", (8,))])
 # slamgpu_pose_edge (include/slamgpu_optimizer.h): one PoseOptimization correspondence.
@@ -47,6 +55,7 @@ BA_OBS_DTYPE = np.dtype([("keyframe", "<i4"), ("u", "<f4"), ("v", "<f4"), ("ur",
                          ("octave", "<i4")])
 assert KP_DTYPE.itemsize == 28 and F2F_QUERY_DTYPE.itemsize == 64 and POSE_EDGE_DTYPE.itemsize == 28
 assert F2F_POSE_DTYPE.itemsize == 72 and MPS_QUERY_DTYPE.itemsize == 80
+assert SIM3_RANSAC_JOB_DTYPE.itemsize == 24 and SIM3_HYP_DTYPE.itemsize == 64
 
 EXPORTS = [
     "slamgpu_create", "slamgpu_destroy", "slamgpu_last_error", "slamgpu_kp_capacity",
@@ -81,6 +90,8 @@ EXPORTS = [
     "slamgpu_search_by_projection_sim3", "slamgpu_search_by_projection_sim3_scratch_bytes",
     "slamgpu_search_by_projection_sim3_device", "slamgpu_search_by_sim3",
     "slamgpu_search_by_sim3_device",
+    # include/slamgpu_sim3solver.h
+    "slamgpu_sim3solver_last_error", "slamgpu_sim3_ransac", "slamgpu_sim3_ransac_device",
     # include/slamgpu_io.h
     "slamgpu_io_last_error", "slamgpu_kitti_load_images", "slamgpu_kitti_image_path",
     "slamgpu_png_info", "slamgpu_png_decode", "slamgpu_imread_png",
@@ -217,6 +228,13 @@ def lib():
                                              C.POINTER(ip)]
             L.slamgpu_imread_png.argtypes = [C.c_char_p, vp, sz, sz, C.POINTER(ip), C.POINTER(ip),
                                              C.POINTER(ip)]
+        if hasattr(L, "slamgpu_sim3_ransac"):  # include/slamgpu_sim3solver.h (absent from older A/B builds)
+            L.slamgpu_sim3solver_last_error.argtypes = []
+            L.slamgpu_sim3solver_last_error.restype = C.c_char_p
+            L.slamgpu_sim3_ransac.argtypes = [vp, vp, vp, vp, ip, vp, ip, vp, ip, ip, ip, vp, vp,
+                                              vp, C.POINTER(ip)]
+            L.slamgpu_sim3_ransac_device.argtypes = [vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip,
+                                                     ip, ip, vp, vp, vp, vp, vp]
         L.slamgpu_optimizer_last_error.argtypes = []
         L.slamgpu_optimizer_last_error.restype = C.c_char_p
         if hasattr(L, "slamgpu_coop_slots_in_use"):  # diagnostic (absent from older A/B builds)
@@ -808,6 +826,183 @@ def optimize_sim3_device(K1, K2, inv_sigma2_1, inv_sigma2_2, d_matches, d_match_
         _ptr(K1), _ptr(K2), _ptr(i1), _ptr(i2), len(i1), _ptr(d_matches), _ptr(d_match_start),
         n_problems, float(th2), int(bool(fix_scale)), _ptr(d_S12), _ptr(d_inlier),
         _ptr(d_n_inliers), _ptr(d_lm_iterations), C.c_void_p(stream) if stream else None))
+
+
+def _s3_check(rc):
+    if rc != 0:
+        raise SlamGpuError(f"slamgpu sim3solver error {rc}: "
+                           f"{lib().slamgpu_sim3solver_last_error().decode()}")
+
+
+def sim3_ransac_device(K1, K2, sigma2_1, sigma2_2, d_matches, n_matches_total, d_draws,
+                       n_draws_total, d_jobs, n_jobs, max_n, max_its, d_hyp, d_inlier_bits,
+                       d_events, d_n_events, stream=None):
+    """slamgpu_sim3_ransac_device: the whole RANSAC schedule of a batch of loop candidates in HBM
+    (jobs SIM3_RANSAC_JOB_DTYPE; hyp [n_jobs][max_its] SIM3_HYP_DTYPE; inlier_bits
+    [n_jobs][max_its][ceil(max_n / 64)] int64/uint64; events [n_jobs][max_its], n_events [n_jobs]
+    int32). sigma2_*: level_sigma_sq, not the inverse."""
+    K1, K2, s1, s2 = _sim3_args(K1, K2, sigma2_1, sigma2_2)
+    _s3_check(lib().slamgpu_sim3_ransac_device(
+        _ptr(K1), _ptr(K2), _ptr(s1), _ptr(s2), len(s1), _ptr(d_matches), int(n_matches_total),
+        _ptr(d_draws), int(n_draws_total), _ptr(d_jobs), int(n_jobs), int(max_n), int(max_its),
+        _ptr(d_hyp), _ptr(d_inlier_bits), _ptr(d_events), _ptr(d_n_events),
+        C.c_void_p(stream) if stream else None))
+
+
+def sim3_ransac(matches, draws, n_its, min_inliers, fix_scale, K1, K2, sigma2_1, sigma2_2):
+    """slamgpu_sim3_ransac (synchronous, one candidate): returns (hyp[n_its] SIM3_HYP_DTYPE,
+    inlier_bits[n_its][ceil(n / 64)] uint64, events[n_events])."""
+    K1, K2, s1, s2 = _sim3_args(K1, K2, sigma2_1, sigma2_2)
+    m = np.ascontiguousarray(matches, dtype=SIM3_MATCH_DTYPE)
+    d = np.ascontiguousarray(draws, np.int32).reshape(-1)
+    n, rows = len(m), max(int(n_its), 1)
+    if len(d) < 3 * int(n_its):
+        raise ValueError("three draws per iteration are needed")
+    hyp = np.zeros(rows, SIM3_HYP_DTYPE)
+    bits = np.zeros((rows, max((n + 63) // 64, 1)), np.uint64)
+    events = np.zeros(rows, np.int32)
+    ne = C.c_int()
+    _s3_check(lib().slamgpu_sim3_ransac(_ptr(K1), _ptr(K2), _ptr(s1), _ptr(s2), len(s1), _ptr(m), n,
+                                        _ptr(d), int(n_its), int(min_inliers),
+                                        int(bool(fix_scale)), _ptr(hyp), _ptr(bits), _ptr(events),
+                                        C.byref(ne)))
+    return hyp[:n_its], bits[:n_its], events[:ne.value].copy()
+
+
+def sim3_ransac_iterations(n, probability=0.99, min_inliers=6, max_its=300):
+    """The effective mRansacMaxIts of Sim3Solver::SetRansacParameters (sim3solver.cpp:127-137):
+    float epsilon, double log / pow, N == minInliers -> 1, max(1, min(...)). A quotient that is
+    not a positive int (epsilon >= 1 or 0) converts to INT_MIN in the reference's build: 1."""
+    import math
+    if min_inliers == n:
+        return max(1, min(1, int(max_its)))
+    if n <= 0:
+        return 1
+    eps = float(np.float32(np.float32(min_inliers) / np.float32(n)))
+    try:
+        its = math.ceil(math.log(1 - probability) / math.log(1 - eps ** 3))
+    except (ValueError, ZeroDivisionError, OverflowError):
+        return 1
+    if not 1 <= its <= 2147483647:
+        return 1
+    return max(1, min(its, int(max_its)))
+
+
+_libc = None
+
+
+def reference_random_int(lo, hi):
+    """DUtils::Random::RandomInt (DUtils/Random.cpp:47-50) on the C library's rand()."""
+    global _libc
+    if _libc is None:
+        _libc = C.CDLL(None)
+    d = hi - lo + 1
+    return int((_libc.rand() / (2147483647 + 1.0)) * d) + lo
+
+
+class Sim3Solver:
+    """The reference's Sim3Solver (src/solvers/sim3solver.h) over gathered correspondences
+    (SIM3_MATCH_DTYPE as Optimizer.OptimizeSim3 takes them; indices1 = mvnIndices1, the pKF1
+    feature of each, n1 = mN1 = len(vpMatched12)). SetRansacParameters draws the WHOLE schedule
+    with random_int(min, max) -- in the order the reference would consume the draws for this
+    solver alone -- and evaluates it in one synchronous device call; iterate / find replay
+    sim3solver.cpp:142-217 over the per-hypothesis counts and events without touching the points
+    again. The constructor only records the reference's default parameters (0.99, 6, 300): they
+    are evaluated by the first iterate if SetRansacParameters was never called."""
+
+    def __init__(self, matches, K1, K2, sigma2_1, sigma2_2, fix_scale=True, indices1=None,
+                 n1=None, random_int=None):
+        self.matches = np.ascontiguousarray(matches, dtype=SIM3_MATCH_DTYPE)
+        self.N = len(self.matches)
+        self.indices1 = np.arange(self.N) if indices1 is None else np.asarray(indices1, np.int64)
+        self.mN1 = self.N if n1 is None else int(n1)
+        self._cam = (K1, K2, sigma2_1, sigma2_2)
+        self.fix_scale = bool(fix_scale)
+        self.random_int = random_int or reference_random_int
+        self._params = (0.99, 6, 300)
+        self._evaluated = False
+        self.mnIterations = 0
+        self.last_k = -1
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        self._params = (probability, minInliers, maxIterations)
+        self.mRansacMinInliers = int(minInliers)
+        self.mRansacMaxIts = sim3_ransac_iterations(self.N, probability, minInliers, maxIterations)
+        self.mnIterations = 0
+        self._evaluated = True
+        self.draws = np.zeros((self.mRansacMaxIts, 3), np.int32)
+        self.hyp = self.bits = self.events = None
+        if self.N < self.mRansacMinInliers or self.N < 3:
+            return  # iterate returns at once (:151-154): nothing is drawn
+        if self.mRansacMaxIts > SIM3_RANSAC_MAX_ITS:
+            raise SlamGpuError(f"maxIterations above {SIM3_RANSAC_MAX_ITS}")
+        for k in range(self.mRansacMaxIts):
+            for i in range(3):
+                self.draws[k, i] = self.random_int(0, self.N - 1 - i)
+        self.hyp, self.bits, self.events = sim3_ransac(
+            self.matches, self.draws, self.mRansacMaxIts, self.mRansacMinInliers, self.fix_scale,
+            *self._cam)
+
+    def _scatter(self, k):
+        vb = np.zeros(self.mN1, bool)
+        row = np.unpackbits(self.bits[k].view(np.uint8), bitorder="little")[:self.N].astype(bool)
+        vb[self.indices1[row]] = True
+        return vb
+
+    def _T12(self, k):
+        h = self.hyp[k]
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = np.float32(h["s12"]) * h["R12"].reshape(3, 3)
+        T[:3, 3] = h["t12"]
+        return T
+
+    def iterate(self, nIterations):
+        """Returns (T12 4x4 f32 or None, bNoMore, vbInliers[mN1], nInliers)."""
+        if not self._evaluated:
+            self.SetRansacParameters(*self._params)
+        vb = np.zeros(self.mN1, bool)
+        self.last_k = -1
+        if self.N < self.mRansacMinInliers:
+            return None, True, vb, 0
+        if self.hyp is None:
+            raise SlamGpuError("fewer than 3 correspondences")
+        start = self.mnIterations
+        end = min(self.mRansacMaxIts, start + max(int(nIterations), 0))
+        j = int(np.searchsorted(self.events, start))
+        if j < len(self.events) and self.events[j] < end:
+            k = int(self.events[j])
+            self.mnIterations = k + 1
+            self.last_k = k
+            return self._T12(k), False, self._scatter(k), int(self.hyp["n_inliers"][k])
+        self.mnIterations = end
+        return None, self.mnIterations >= self.mRansacMaxIts, vb, 0
+
+    def find(self):
+        """Returns (T12 or None, vbInliers12, nInliers)."""
+        if not self._evaluated:
+            self.SetRansacParameters(*self._params)
+        T, _, vb, n = self.iterate(self.mRansacMaxIts)
+        return T, vb, n
+
+    def _best(self):
+        """The iteration mBest* hold: the last one, among those run, that reached the running
+        maximum (the >= of :186); None before the first."""
+        if not self._evaluated or self.hyp is None or self.mnIterations == 0:
+            return None
+        c = self.hyp["n_inliers"][:self.mnIterations]
+        return int(len(c) - 1 - np.argmax(c[::-1]))
+
+    def GetEstimatedRotation(self):
+        k = self._best()
+        return None if k is None else self.hyp["R12"][k].reshape(3, 3).copy()
+
+    def GetEstimatedTranslation(self):
+        k = self._best()
+        return None if k is None else self.hyp["t12"][k].copy()
+
+    def GetEstimatedScale(self):
+        k = self._best()
+        return None if k is None else float(self.hyp["s12"][k])
 
 
 def pose_optimization_device(cam, inv_sigma2, d_edges, d_edge_start, n_frames, d_Tcw, d_outlier,
