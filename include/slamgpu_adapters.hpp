@@ -29,6 +29,7 @@
 #include "slamgpu_kfmatch.h"
 #include "slamgpu_loopmatch.h"
 #include "slamgpu_optimizer.h"
+#include "slamgpu_pnpsolver.h"
 #include "slamgpu_sim3solver.h"
 
 namespace slamgpu_adapter {
@@ -1128,6 +1129,193 @@ class Sim3SolverCore {
   std::vector<int32_t> draws_, events_;
   std::vector<slamgpu_sim3_hyp> hyp_;
   std::vector<uint64_t> bits_;
+};
+
+// ---- PnPsolver (src/solvers/pnp_solver.h, pnp_solver.cpp), Tracker::Relocalization
+// (tracker.cpp:826-991) ---------------------------------------------------------------------------
+// The effective mRansacMinInliers and mRansacMaxIts of SetRansacParameters (:87-105), host libm
+// as the reference: int(N * float epsilon), the two lower bounds, the float epsilon raised to
+// minInliers / N, std::pow(float, int) and std::log in double, N == minInliers -> 1. A quotient
+// that is no positive int is what the reference's x86 build converts to INT_MIN. The sample is
+// four points: any other minSet throws.
+struct PnpRansacParameters {
+  int min_inliers, max_its;
+};
+inline PnpRansacParameters pnp_ransac_parameters(int N, double probability, int minInliers,
+                                                 int maxIterations, int minSet, float epsilon) {
+  if (minSet != 4)
+    throw std::invalid_argument("slamgpu: PnPsolver minSet " + std::to_string(minSet) +
+                                " is not supported, the sample is 4 points");
+  int nMinInliers = (int)(N * epsilon);
+  if (nMinInliers < minInliers) nMinInliers = minInliers;
+  if (nMinInliers < minSet) nMinInliers = minSet;
+  if (epsilon < (float)nMinInliers / N) epsilon = (float)nMinInliers / N;
+  int nIterations;
+  if (nMinInliers == N) {
+    nIterations = 1;
+  } else {
+    const double v =
+        std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3)));
+    nIterations = v >= 1.0 && v <= 2147483647.0 ? (int)v : INT_MIN;
+  }
+  return {nMinInliers, std::max(1, std::min(nIterations, maxIterations))};
+}
+
+// The reference class's surface over the views. The constructor does the gather of :32-54
+// (mvP2D, the octave mvSigma2 is looked up with, mvP3Dw, mvKeyPointIndices; map points that are
+// absent or bad are skipped) and, unlike the reference's, evaluates nothing: the default
+// parameters (0.99, 8, 300, 4, 0.4, 5.991) are evaluated by the first iterate if
+// SetRansacParameters was never called. SetRansacParameters draws the WHOLE schedule with the
+// functor -- in the order the reference would consume the draws for this solver alone (see
+// Sim3SolverCore) -- and makes the one synchronous call. iterate / find then replay :112-211 from
+// the counts, the running bests, the refined rows and the events. The loop of :135 runs while
+// mnIterations < mRansacMaxIts OR the call's own count < nIterations, so a call that starts near
+// the end runs past the schedule: the core appends draws and evaluates the longer schedule again
+// (the prefix is the same draws, hence the same rows; nothing is carried in).
+class PnPSolverCore {
+ public:
+  using RandomInt = std::function<int(int, int)>;
+
+  PnPSolverCore(const FrameView& F, const MapPointView* mps, const int32_t* vpMapPointMatches,
+                int n_matches, const float K[4], const float* sigma2, int nlevels,
+                RandomInt random_int = reference_random_int)
+      : n_kp_(n_matches), nlevels_(nlevels), sigma2_(sigma2, sigma2 + nlevels),
+        random_int_(std::move(random_int)) {
+    std::memcpy(K_, K, sizeof K_);
+    for (int i = 0; i < n_matches; ++i) {
+      const int mp = vpMapPointMatches[i];
+      if (mp < 0 || mps[mp].bad) continue;
+      const slamgpu_keypoint& kp = F.undist_kps[i];
+      slamgpu_pnp_match c;
+      c.xw[0] = mps[mp].xyz[0], c.xw[1] = mps[mp].xyz[1], c.xw[2] = mps[mp].xyz[2];
+      c.u = kp.x, c.v = kp.y;
+      c.octave = kp.octave;
+      matches_.push_back(c);
+      indices_.push_back(i);
+    }
+  }
+
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300,
+                           int minSet = 4, float epsilon = 0.4f, float th2 = 5.991f) {
+    prob_ = probability, min_inliers_arg_ = minInliers, max_its_arg_ = maxIterations;
+    min_set_ = minSet, epsilon_ = epsilon, th2_ = th2;
+    const int N = (int)matches_.size();
+    const PnpRansacParameters p =
+        pnp_ransac_parameters(N, probability, minInliers, maxIterations, minSet, epsilon);
+    min_inliers_ = p.min_inliers, max_its_ = p.max_its;
+    iterations_ = 0;
+    evaluated_ = true;
+    draws_.clear();
+    hyp_.clear(), refined_.clear(), bits_.clear(), refined_bits_.clear(), events_.clear();
+    if (N < min_inliers_) return;  // iterate returns at once (:126-130): nothing is drawn
+    extend(max_its_);
+  }
+
+  // iterate (:118-211). true when a pose is returned: Tcw (4x4 row-major) is mRefinedTcw, or
+  // mBestTcw at exhaustion; false for the reference's empty cv::Mat.
+  bool iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers,
+               float Tcw[16]) {
+    if (!evaluated_)
+      SetRansacParameters(prob_, min_inliers_arg_, max_its_arg_, min_set_, epsilon_, th2_);
+    bNoMore = false;
+    vbInliers.clear();
+    nInliers = 0;
+    const int N = (int)matches_.size();
+    if (N < min_inliers_) {
+      bNoMore = true;
+      return false;
+    }
+    const int start = iterations_;
+    const int end = std::max(max_its_, start + std::max(nIterations, 0));  // the || of :135
+    for (;;) {
+      size_t j = 0;
+      while (j < events_.size() && events_[j] < start) ++j;
+      if (j < events_.size() && events_[j] < end) {
+        const int k = events_[j], b = hyp_[k].best;
+        iterations_ = k + 1;
+        give(refined_[b], &refined_bits_[(size_t)b * words_], vbInliers, nInliers, Tcw);
+        return true;
+      }
+      if ((int)hyp_.size() >= end) break;
+      extend(end);
+    }
+    iterations_ = end;  // >= mRansacMaxIts (:194-196)
+    bNoMore = true;
+    const int b = hyp_[end - 1].best;
+    if (b < 0) return false;  // mnBestInliers < mRansacMinInliers
+    give(hyp_[b], &bits_[(size_t)b * words_], vbInliers, nInliers, Tcw);
+    return true;
+  }
+  // find (:112-116)
+  bool find(std::vector<bool>& vbInliers, int& nInliers, float Tcw[16]) {
+    if (!evaluated_)
+      SetRansacParameters(prob_, min_inliers_arg_, max_its_arg_, min_set_, epsilon_, th2_);
+    bool flag;
+    return iterate(max_its_, flag, vbInliers, nInliers, Tcw);
+  }
+
+  const std::vector<slamgpu_pnp_match>& matches() const { return matches_; }
+  const std::vector<int32_t>& indices() const { return indices_; }  // mvKeyPointIndices
+  const std::vector<int32_t>& draws() const { return draws_; }
+  int min_inliers() const { return min_inliers_; }    // the effective mRansacMinInliers
+  int max_iterations() const { return max_its_; }     // the effective mRansacMaxIts
+  int iterations() const { return iterations_; }      // mnIterations
+  int device_calls() const { return device_calls_; }  // 1, and one more per schedule extension
+
+ private:
+  // Draws up to n_its iterations and evaluates the schedule.
+  void extend(int n_its) {
+    if (n_its > SLAMGPU_PNP_RANSAC_MAX_ITS)
+      throw std::runtime_error("slamgpu: PnPsolver " + std::to_string(n_its) +
+                               " iterations > SLAMGPU_PNP_RANSAC_MAX_ITS");
+    const int N = (int)matches_.size();
+    for (int k = (int)draws_.size() / 4; k < n_its; ++k)
+      for (int i = 0; i < 4; ++i) draws_.push_back(random_int_(0, N - 1 - i));
+    words_ = SLAMGPU_PNP_MASK_WORDS(N);
+    hyp_.assign(n_its, slamgpu_pnp_hyp{});
+    refined_.assign(n_its, slamgpu_pnp_hyp{});
+    bits_.assign((size_t)n_its * words_, 0);
+    refined_bits_.assign((size_t)n_its * words_, 0);
+    events_.assign(n_its, 0);
+    int ne = 0;
+    ++device_calls_;
+    throw_if(slamgpu_pnp_ransac(K_, sigma2_.data(), nlevels_, th2_, matches_.data(), N,
+                                draws_.data(), n_its, min_inliers_, hyp_.data(), bits_.data(),
+                                refined_.data(), refined_bits_.data(), events_.data(), &ne),
+             slamgpu_pnpsolver_last_error);
+    events_.resize(ne);
+  }
+
+  void give(const slamgpu_pnp_hyp& h, const uint64_t* bits, std::vector<bool>& vbInliers,
+            int& nInliers, float Tcw[16]) const {
+    nInliers = h.n_inliers;
+    vbInliers.assign(n_kp_, false);
+    for (size_t i = 0; i < matches_.size(); ++i)
+      if (bits[i / 64] >> (i % 64) & 1) vbInliers[indices_[i]] = true;
+    for (int r = 0; r < 3; ++r) {
+      for (int c = 0; c < 3; ++c) Tcw[4 * r + c] = h.Rcw[3 * r + c];
+      Tcw[4 * r + 3] = h.tcw[r];
+      Tcw[12 + r] = 0.0f;
+    }
+    Tcw[15] = 1.0f;
+  }
+
+  int n_kp_, nlevels_;
+  float K_[4];
+  std::vector<float> sigma2_;
+  RandomInt random_int_;
+  std::vector<slamgpu_pnp_match> matches_;
+  std::vector<int32_t> indices_;
+  double prob_ = 0.99;
+  int min_inliers_arg_ = 8, max_its_arg_ = 300, min_set_ = 4;
+  float epsilon_ = 0.4f, th2_ = 5.991f;
+  int min_inliers_ = 8, max_its_ = 300;
+  bool evaluated_ = false;
+  int iterations_ = 0;  // mnIterations
+  int words_ = 0, device_calls_ = 0;
+  std::vector<int32_t> draws_, events_;
+  std::vector<slamgpu_pnp_hyp> hyp_, refined_;
+  std::vector<uint64_t> bits_, refined_bits_;
 };
 
 // ---- Optimizer::BundleAdjustment (optimizer.cpp:33-207), GlobalBundleAdjustemnt (:18-31) ----

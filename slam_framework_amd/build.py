@@ -41,6 +41,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_geometry_check()
         build_host_stage_check()
         build_sim3solver_adapter_check()
+        build_pnpsolver_adapter_check()
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -70,6 +71,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_geometry_check()
     build_host_stage_check()
     build_sim3solver_adapter_check()
+    build_pnpsolver_adapter_check()
     return LIB
 
 
@@ -129,6 +131,25 @@ def build_sim3solver_adapter_check() -> str:
                     "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", SIM3SOLVER_ADAPTER_BIN],
                    check=True)
     return SIM3SOLVER_ADAPTER_BIN
+
+
+PNPSOLVER_ADAPTER_SRC = os.path.join(ROOT, "tests", "pnpsolver_adapter_check.cpp")
+PNPSOLVER_ADAPTER_BIN = os.path.join(ROOT, "tests", "pnpsolver_adapter_check")
+
+
+def build_pnpsolver_adapter_check() -> str:
+    """g++ build of tests/pnpsolver_adapter_check.cpp: PnPSolverCore of
+    include/slamgpu_adapters.hpp (the gather, the eager draws, the iterate / find replay with its
+    schedule extension) driven from C++ against libslamgpu.so."""
+    deps = [PNPSOLVER_ADAPTER_SRC, LIB] + glob.glob(os.path.join(ROOT, "include", "*.h*"))
+    if os.path.exists(PNPSOLVER_ADAPTER_BIN) and os.path.getmtime(PNPSOLVER_ADAPTER_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return PNPSOLVER_ADAPTER_BIN
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I",
+                    os.path.join(ROOT, "include"), PNPSOLVER_ADAPTER_SRC, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", PNPSOLVER_ADAPTER_BIN],
+                   check=True)
+    return PNPSOLVER_ADAPTER_BIN
 
 
 GEOMETRY_SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")

@@ -1,7 +1,7 @@
 // host_stage.h -- the per-thread staging buffer and stream of the synchronous C-ABI wrappers
-// (optimizer, BoW, kfmatch, loopmatch, sim3solver). A wrapper takes a StageLease, lays its arrays out with a
-// StageLayout (stage_layout.h), reserves layout.size() bytes, uploads, launches its *_device form
-// on the stage's stream, downloads and synchronises before it returns.
+// (optimizer, BoW, kfmatch, loopmatch, sim3solver, pnpsolver). A wrapper takes a StageLease, lays
+// its arrays out with a StageLayout (stage_layout.h), reserves layout.size() bytes, uploads,
+// launches its *_device form on the stage's stream, downloads and synchronises before it returns.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -15,6 +15,7 @@
 #include "../../include/slamgpu_bow.h"
 #include "../../include/slamgpu_loopmatch.h"
 #include "../../include/slamgpu_optimizer.h"
+#include "../../include/slamgpu_pnpsolver.h"
 #include "../../include/slamgpu_sim3solver.h"
 #include "host_common.h"
 
@@ -153,6 +154,19 @@ inline Sim3RansacLayout layout_sim3_ransac(StageLayout& L, size_t n, size_t n_it
   return {L.take<slamgpu_sim3_match>(n), L.take<int32_t>(3 * n_its),
           L.take<slamgpu_sim3_ransac_job>(1), L.take<slamgpu_sim3_hyp>(n_its),
           L.take<uint64_t>(n_its * SLAMGPU_SIM3_MASK_WORDS(n)), L.take<int32_t>(n_its),
+          L.take<int32_t>(1)};
+}
+
+// The RANSAC EPnP solver of one candidate: n correspondences, n_its iterations of 4 draws; the
+// mask rows (hypotheses and refined) are SLAMGPU_PNP_MASK_WORDS(n) words each.
+struct PnpRansacLayout {
+  size_t matches, draws, job, hyp, bits, refined, refined_bits, events, n_events;
+};
+inline PnpRansacLayout layout_pnp_ransac(StageLayout& L, size_t n, size_t n_its) {
+  return {L.take<slamgpu_pnp_match>(n), L.take<int32_t>(4 * n_its),
+          L.take<slamgpu_pnp_ransac_job>(1), L.take<slamgpu_pnp_hyp>(n_its),
+          L.take<uint64_t>(n_its * SLAMGPU_PNP_MASK_WORDS(n)), L.take<slamgpu_pnp_hyp>(n_its),
+          L.take<uint64_t>(n_its * SLAMGPU_PNP_MASK_WORDS(n)), L.take<int32_t>(n_its),
           L.take<int32_t>(1)};
 }
 

@@ -44,6 +44,18 @@ SIM3_HYP_DTYPE = np.dtype([("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "
                            ("n_inliers", "<i4"), ("pad", "<i4", (2,))])
 SIM3_MAX_MATCHES = 4096
 SIM3_RANSAC_MAX_ITS = 300
+# slamgpu_pnp_match / slamgpu_pnp_ransac_job / slamgpu_pnp_hyp (include/slamgpu_pnpsolver.h): one
+# correspondence of the RANSAC EPnP solver (mvP3Dw, mvP2D, the keypoint's octave), one candidate,
+# one hypothesis or refined pose (mRi, mti as float, the inlier count, the running best).
+PNP_MATCH_DTYPE = np.dtype([("xw", "<f4", (3,)), ("u", "<f4"), ("v", "<f4"), ("octave", "<i4")])
+PNP_JOB_DTYPE = np.dtype([("match_begin", "<i4"), ("n", "<i4"), ("draw_begin", "<i4"),
+                          ("n_its", "<i4"), ("min_inliers", "<i4"), ("pad", "<i4")])
+PNP_HYP_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("n_inliers", "<i4"),
+                          ("best", "<i4"), ("pad", "<i4", (2,))])
+PNP_MAX_MATCHES = 4096
+PNP_RANSAC_MAX_ITS = 512
+assert PNP_MATCH_DTYPE.itemsize == 24 and PNP_JOB_DTYPE.itemsize == 24
+assert PNP_HYP_DTYPE.itemsize == 64
 # slamgpu_sim3_edge (include/slamgpu_optimizer.h): one EdgeSim3 of the essential graph.
 SIM3_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("pad", "<i4", (2,)), ("Sji", "<f8", (8,))])
 # slamgpu_pose_edge (include/slamgpu_optimizer.h): one PoseOptimization correspondence.
@@ -92,6 +104,8 @@ EXPORTS = [
     "slamgpu_search_by_sim3_device",
     # include/slamgpu_sim3solver.h
     "slamgpu_sim3solver_last_error", "slamgpu_sim3_ransac", "slamgpu_sim3_ransac_device",
+    # include/slamgpu_pnpsolver.h
+    "slamgpu_pnpsolver_last_error", "slamgpu_pnp_ransac", "slamgpu_pnp_ransac_device",
     # include/slamgpu_io.h
     "slamgpu_io_last_error", "slamgpu_kitti_load_images", "slamgpu_kitti_image_path",
     "slamgpu_png_info", "slamgpu_png_decode", "slamgpu_imread_png",
@@ -235,6 +249,13 @@ def lib():
                                               vp, C.POINTER(ip)]
             L.slamgpu_sim3_ransac_device.argtypes = [vp, vp, vp, vp, ip, vp, ip, vp, ip, vp, ip,
                                                      ip, ip, vp, vp, vp, vp, vp]
+        if hasattr(L, "slamgpu_pnp_ransac"):  # include/slamgpu_pnpsolver.h (absent from older A/B builds)
+            L.slamgpu_pnpsolver_last_error.argtypes = []
+            L.slamgpu_pnpsolver_last_error.restype = C.c_char_p
+            L.slamgpu_pnp_ransac.argtypes = [vp, vp, ip, fp, vp, ip, vp, ip, ip, vp, vp, vp, vp,
+                                             vp, C.POINTER(ip)]
+            L.slamgpu_pnp_ransac_device.argtypes = [vp, vp, ip, fp, vp, ip, vp, ip, vp, ip, ip,
+                                                    ip, vp, vp, vp, vp, vp, vp, vp]
         L.slamgpu_optimizer_last_error.argtypes = []
         L.slamgpu_optimizer_last_error.restype = C.c_char_p
         if hasattr(L, "slamgpu_coop_slots_in_use"):  # diagnostic (absent from older A/B builds)
@@ -1003,6 +1024,182 @@ class Sim3Solver:
     def GetEstimatedScale(self):
         k = self._best()
         return None if k is None else float(self.hyp["s12"][k])
+
+
+def _pnp_check(rc):
+    if rc != 0:
+        raise SlamGpuError(f"slamgpu pnpsolver error {rc}: "
+                           f"{lib().slamgpu_pnpsolver_last_error().decode()}")
+
+
+def _pnp_args(K, sigma2):
+    K = np.ascontiguousarray(K, np.float32).reshape(-1)
+    if len(K) != 4:
+        raise ValueError("K = (fx, fy, cx, cy)")
+    return K, np.ascontiguousarray(sigma2, np.float32).reshape(-1)
+
+
+def pnp_ransac_device(K, sigma2, th2, d_matches, n_matches_total, d_draws, n_draws_total, d_jobs,
+                      n_jobs, max_n, max_its, d_hyp, d_inlier_bits, d_refined, d_refined_bits,
+                      d_events, d_n_events, stream=None):
+    """slamgpu_pnp_ransac_device: the whole RANSAC EPnP schedule of a batch of relocalisation
+    candidates in HBM (matches PNP_MATCH_DTYPE; jobs PNP_JOB_DTYPE; hyp and refined
+    [n_jobs][max_its] PNP_HYP_DTYPE; inlier_bits and refined_bits
+    [n_jobs][max_its][ceil(max_n / 64)] int64/uint64; events [n_jobs][max_its], n_events [n_jobs]
+    int32). sigma2: level_sigma_sq, not the inverse."""
+    K, s = _pnp_args(K, sigma2)
+    _pnp_check(lib().slamgpu_pnp_ransac_device(
+        _ptr(K), _ptr(s), len(s), float(th2), _ptr(d_matches), int(n_matches_total), _ptr(d_draws),
+        int(n_draws_total), _ptr(d_jobs), int(n_jobs), int(max_n), int(max_its), _ptr(d_hyp),
+        _ptr(d_inlier_bits), _ptr(d_refined), _ptr(d_refined_bits), _ptr(d_events),
+        _ptr(d_n_events), C.c_void_p(stream) if stream else None))
+
+
+def pnp_ransac(matches, draws, n_its, min_inliers, K, sigma2, th2=5.991):
+    """slamgpu_pnp_ransac (synchronous, one candidate): returns (hyp[n_its] PNP_HYP_DTYPE,
+    inlier_bits[n_its][ceil(n / 64)] uint64, refined[n_its], refined_bits[n_its][...],
+    events[n_events])."""
+    K, s = _pnp_args(K, sigma2)
+    m = np.ascontiguousarray(matches, dtype=PNP_MATCH_DTYPE)
+    d = np.ascontiguousarray(draws, np.int32).reshape(-1)
+    n, rows = len(m), max(int(n_its), 1)
+    if len(d) < 4 * int(n_its):
+        raise ValueError("four draws per iteration are needed")
+    words = max((n + 63) // 64, 1)
+    hyp, refined = np.zeros(rows, PNP_HYP_DTYPE), np.zeros(rows, PNP_HYP_DTYPE)
+    bits, rbits = np.zeros((rows, words), np.uint64), np.zeros((rows, words), np.uint64)
+    events = np.zeros(rows, np.int32)
+    ne = C.c_int()
+    _pnp_check(lib().slamgpu_pnp_ransac(_ptr(K), _ptr(s), len(s), float(th2), _ptr(m), n, _ptr(d),
+                                        int(n_its), int(min_inliers), _ptr(hyp), _ptr(bits),
+                                        _ptr(refined), _ptr(rbits), _ptr(events), C.byref(ne)))
+    return hyp[:n_its], bits[:n_its], refined[:n_its], rbits[:n_its], events[:ne.value].copy()
+
+
+def pnp_ransac_parameters(N, probability=0.99, minInliers=8, maxIterations=300, minSet=4,
+                          epsilon=0.4):
+    """The effective (mRansacMinInliers, mRansacMaxIts) of PnPsolver::SetRansacParameters
+    (pnp_solver.cpp:87-105): int(N * float epsilon), the two lower bounds, the float epsilon
+    raised to minInliers / N, pow(epsilon, 3) and log in double, N == minInliers -> 1. A quotient
+    that is not a positive int converts to INT_MIN in the reference's build: 1."""
+    import math
+    if minSet != 4:
+        raise SlamGpuError(f"PnPsolver: minSet {minSet} is not supported, the sample is 4 points")
+    eps = np.float32(epsilon)
+    n_min = max(int(np.float32(N) * eps), int(minInliers), int(minSet))
+    if N > 0 and eps < np.float32(n_min) / np.float32(N):
+        eps = np.float32(n_min) / np.float32(N)
+    if n_min == N:
+        return n_min, max(1, min(1, int(maxIterations)))
+    try:
+        its = math.ceil(math.log(1 - probability) / math.log(1 - float(eps) ** 3))
+    except (ValueError, ZeroDivisionError, OverflowError):
+        return n_min, 1
+    if not 1 <= its <= 2147483647:
+        return n_min, 1
+    return n_min, max(1, min(its, int(maxIterations)))
+
+
+class PnPsolver:
+    """The reference's PnPsolver (src/solvers/pnp_solver.h) over gathered correspondences
+    (PNP_MATCH_DTYPE; indices = mvKeyPointIndices, the frame keypoint of each; n_kp =
+    len(vpMapPointMatches) for the scatter). SetRansacParameters draws the WHOLE schedule with
+    random_int(min, max) -- in the order the reference would consume the draws for this solver
+    alone -- and evaluates it in one synchronous device call; iterate / find replay
+    pnp_solver.cpp:112-211 over the counts, the running bests, the refined rows and the events.
+    The loop of :135 runs while mnIterations < mRansacMaxIts OR the call's own count < nIterations:
+    a call that starts near the end runs past the schedule, so the solver appends draws and
+    evaluates the longer schedule again (the prefix is the same draws, hence the same rows). The
+    constructor only records the reference's default parameters: they are evaluated by the first
+    iterate if SetRansacParameters was never called."""
+
+    def __init__(self, matches, K, sigma2, indices=None, n_kp=None, random_int=None):
+        self.matches = np.ascontiguousarray(matches, dtype=PNP_MATCH_DTYPE)
+        self.N = len(self.matches)
+        self.indices = np.arange(self.N) if indices is None else np.asarray(indices, np.int64)
+        self.n_kp = self.N if n_kp is None else int(n_kp)
+        self._cam = (K, sigma2)
+        self.random_int = random_int or reference_random_int
+        self._params = (0.99, 8, 300, 4, 0.4, 5.991)
+        self._evaluated = False
+        self.mnIterations = 0
+        self.device_calls = 0
+
+    def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=4,
+                            epsilon=0.4, th2=5.991):
+        self._params = (probability, minInliers, maxIterations, minSet, epsilon, th2)
+        self.mRansacMinInliers, self.mRansacMaxIts = pnp_ransac_parameters(
+            self.N, probability, minInliers, maxIterations, minSet, epsilon)
+        self.th2 = float(th2)
+        self.mnIterations = 0
+        self._evaluated = True
+        self.draws = np.zeros((0, 4), np.int32)
+        self.hyp = self.bits = self.refined = self.refined_bits = self.events = None
+        if self.N < self.mRansacMinInliers:
+            return  # iterate returns at once (:126-130): nothing is drawn
+        self._extend(self.mRansacMaxIts)
+
+    def _extend(self, n_its):
+        """Draws up to n_its iterations and evaluates the schedule."""
+        if n_its > PNP_RANSAC_MAX_ITS:
+            raise SlamGpuError(f"PnPsolver: {n_its} iterations > PNP_RANSAC_MAX_ITS "
+                               f"({PNP_RANSAC_MAX_ITS})")
+        more = np.zeros((n_its - len(self.draws), 4), np.int32)
+        for k in range(len(more)):
+            for i in range(4):
+                more[k, i] = self.random_int(0, self.N - 1 - i)
+        self.draws = np.concatenate([self.draws, more])
+        self.hyp, self.bits, self.refined, self.refined_bits, self.events = pnp_ransac(
+            self.matches, self.draws, n_its, self.mRansacMinInliers, *self._cam, self.th2)
+        self.device_calls += 1
+
+    def _scatter(self, row):
+        vb = np.zeros(self.n_kp, bool)
+        on = np.unpackbits(row.view(np.uint8), bitorder="little")[:self.N].astype(bool)
+        vb[self.indices[on]] = True
+        return vb
+
+    @staticmethod
+    def _Tcw(h):
+        T = np.eye(4, dtype=np.float32)
+        T[:3, :3] = h["Rcw"].reshape(3, 3)
+        T[:3, 3] = h["tcw"]
+        return T
+
+    def iterate(self, nIterations):
+        """Returns (Tcw 4x4 f32 or None, bNoMore, vbInliers[n_kp], nInliers)."""
+        if not self._evaluated:
+            self.SetRansacParameters(*self._params)
+        vb = np.zeros(self.n_kp, bool)
+        if self.N < self.mRansacMinInliers:
+            return None, True, vb, 0
+        start = self.mnIterations
+        end = max(self.mRansacMaxIts, start + max(int(nIterations), 0))  # the || of :135
+        while True:
+            have = len(self.draws)
+            j = int(np.searchsorted(self.events, start))
+            if j < len(self.events) and self.events[j] < end:
+                k = int(self.events[j])
+                b = int(self.hyp["best"][k])
+                self.mnIterations = k + 1
+                return (self._Tcw(self.refined[b]), False, self._scatter(self.refined_bits[b]),
+                        int(self.refined["n_inliers"][b]))
+            if have >= end:
+                break
+            self._extend(end)
+        self.mnIterations = end  # >= mRansacMaxIts >= 1: bNoMore (:194-196)
+        b = int(self.hyp["best"][end - 1])
+        if b >= 0:  # mnBestInliers >= mRansacMinInliers (:197)
+            return (self._Tcw(self.hyp[b]), True, self._scatter(self.bits[b]),
+                    int(self.hyp["n_inliers"][b]))
+        return None, True, vb, 0
+
+    def find(self):
+        """Returns (Tcw or None, vbInliers, nInliers)."""
+        if not self._evaluated:
+            self.SetRansacParameters(*self._params)
+        T, _, vb, n = self.iterate(self.mRansacMaxIts)
+        return T, vb, n
 
 
 def pose_optimization_device(cam, inv_sigma2, d_edges, d_edge_start, n_frames, d_Tcw, d_outlier,
