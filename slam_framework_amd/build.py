@@ -42,6 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_host_stage_check()
         build_sim3solver_adapter_check()
         build_pnpsolver_adapter_check()
+        build_device_math_check()
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -72,6 +73,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_host_stage_check()
     build_sim3solver_adapter_check()
     build_pnpsolver_adapter_check()
+    build_device_math_check()
     return LIB
 
 
@@ -194,6 +196,29 @@ def build_host_stage_check() -> str:
                     HOST_STAGE_SRC, "-o", tmp], check=True)
     os.replace(tmp, HOST_STAGE_BIN)
     return HOST_STAGE_BIN
+
+
+DEVICE_MATH_SRCS = [os.path.join(ROOT, "tests", n) for n in (
+    "device_math_check.hip", "device_math_check_sim3.hip", "device_math_check_eg.hip")]
+DEVICE_MATH_BIN = os.path.join(ROOT, "tests", "device_math_check")
+
+
+def build_device_math_check() -> str:
+    """hipcc build of tests/device_math_check*.hip with the library's own FLAGS: a stand-alone
+    program that includes pose_kernels.hip, sim3_kernels.hip, eg_kernels.hip and the device
+    headers (one translation unit per .hip) and runs their helpers one case per thread. Linked to
+    libslamgpu.so only for the symbols the included launchers refer to."""
+    deps = DEVICE_MATH_SRCS + [os.path.join(ROOT, "tests", "device_math_check.h"), LIB]
+    deps += glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip"))
+    deps += glob.glob(os.path.join(ROOT, "include", "*.h"))
+    if os.path.exists(DEVICE_MATH_BIN) and os.path.getmtime(DEVICE_MATH_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return DEVICE_MATH_BIN
+    tmp = DEVICE_MATH_BIN + ".tmp"
+    subprocess.run([HIPCC, *FLAGS, *DEVICE_MATH_SRCS, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", tmp], check=True)
+    os.replace(tmp, DEVICE_MATH_BIN)
+    return DEVICE_MATH_BIN
 
 
 if __name__ == "__main__":
