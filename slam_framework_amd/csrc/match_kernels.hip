@@ -21,10 +21,6 @@
 
 namespace slamgpu {
 
-#ifndef STEREO_LANES  // lanes per left keypoint in stereo_match (32: two per wave, 16: four)
-#define STEREO_LANES 16
-#endif
-
 constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;
 constexpr uint64_t kNoKey = ~0ull;
 
@@ -33,16 +29,6 @@ __device__ __forceinline__ int hamming32(const uint8_t* a, const uint8_t* b) {
   const uint64_t* pb = reinterpret_cast<const uint64_t*>(b);
   return __popcll(pa[0] ^ pb[0]) + __popcll(pa[1] ^ pb[1]) + __popcll(pa[2] ^ pb[2]) +
          __popcll(pa[3] ^ pb[3]);
-}
-
-__device__ __forceinline__ const uint8_t* level_img(const ImageBatch& b, const OrbGeom* g,
-                                                    int img, int level, int* pitch) {
-  if (level == 0) {
-    *pitch = b.in_pitch;
-    return batch_image(b, img);
-  }
-  *pitch = g->lv[level].pitch;
-  return b.pyr + (int64_t)img * g->pyr_bytes + g->lv[level].offset;
 }
 
 // NT-thread exclusive scan of arr[0..n) in place; returns the total. wsum: NT / 64 ints.
@@ -175,9 +161,10 @@ __global__ __launch_bounds__(NT) void stereo_rows_kernel(const OrbGeom* __restri
   stereo_rows_body<NT>(blockIdx.x, g, ext, nrows, ws, err);
 }
 
-// One left keypoint per G lanes (G = 32: two per wave; G = 16: four): the kernel is a chain of
-// dependent loads per keypoint (row table -> candidates -> descriptors -> SAD windows), so several
-// independent chains per wave hide the latency at the same occupancy.
+// One left keypoint per G = 16 lanes, four per wave: the Hamming stage is a chain of dependent
+// loads per keypoint (row table -> candidates -> descriptors), so several independent chains per
+// wave hide the latency at the same occupancy; in the SAD stage the 16 lanes are one DPP row, one
+// lane per window row.
 template <int G>
 __device__ __forceinline__ uint32_t group_min(uint32_t v) {
 #pragma unroll
@@ -188,26 +175,37 @@ __device__ __forceinline__ uint32_t group_min(uint32_t v) {
   return v;
 }
 
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
+
+// The u16 pair (byte p, byte p + 1) of the byte string e[0], e[1], ... (little-endian dwords),
+// p a constant: one v_perm, its high bytes the selector's constant zero (0x0c).
+__device__ __forceinline__ uint32_t byte_pair(const uint32_t* e, int p) {
+  const int q = p >> 2;
+  switch (p & 3) {
+    case 0: return __builtin_amdgcn_perm(0u, e[q], 0x0c010c00u);
+    case 1: return __builtin_amdgcn_perm(0u, e[q], 0x0c020c01u);
+    case 2: return __builtin_amdgcn_perm(0u, e[q], 0x0c030c02u);
+    default: return __builtin_amdgcn_perm(e[q + 1], e[q], 0x0c040c03u);
+  }
+}
+
 template <int G>
 __global__ __launch_bounds__(256) void stereo_match_kernel(ImageBatch b,
                                                            const OrbGeom* __restrict__ g,
                                                            FrameKps ext, Camera cam, int nrows,
                                                            StereoWorkspace ws, StereoOut out) {
+  static_assert(G == 16, "the SAD stage puts a keypoint's 11 window rows on one 16-lane DPP row");
   constexpr int NPW = 64 / G;  // keypoints per wave
-  constexpr int kRounds = (121 + G - 1) / G;
   int f, bx;
   xcd_image_block(&f, &bx);  // a frame's work-groups share one XCD's L2 (its right keypoints)
-  const int lane = threadIdx.x & 63, grp = lane / G, hl = lane % G;
-  const int iL = (bx * 4 + wave_id()) * NPW + grp;
   const int il = 2 * f, ir = 2 * f + 1;
   const int nl = ext.n[il * ext.n_stride];
-  const int64_t o = (int64_t)f * g->kp_cap + iL;
-  bool ok = iL < nl;
-  if (ok && hl == 0) {
-    out.u_right[o] = -1.0f;
-    out.depth[o] = -1.0f;
-    ws.sad[o] = -1;
-  }
+  if (bx * 4 * NPW >= nl) return;  // the whole work-group
+  const int lane = threadIdx.x & 63, grp = lane / G, hl = lane % G;
+  const int iL = (bx * 4 + wave_id()) * NPW + grp;
+  const bool valid = iL < nl;
+  bool ok = valid;
   KeyPoint kpL{};
   if (ok) kpL = ext.kps[il * ext.stride + iL];
   const int levelL = kpL.octave;
@@ -299,109 +297,124 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(ImageBatch b,
   const int yc = (int)scaledvL, xcl = (int)scaleduL, xcr = (int)scaleduR0;
   // windows the reference would reject with a cv::Mat ROI assertion are treated as no match
   ok = ok && !(yc - w < 0 || yc + w >= LG.h || xcl - w < 0 || xcl + w >= LG.w || xcr - L - w < 0);
-  // SAD of the 11 window offsets: the 121 (offset, row) pairs over the group (kRounds rounds),
-  // each lane summing one 11-pixel row; rows are then summed per offset through LDS. The window
-  // bytes (left: columns xcl-5..xcl+5, right: xcr-10..xcr+10, rows yc-5..yc+5) are first staged
-  // into LDS with dword loads (11 dwords per row: 4 left + 7 right); dwords past a row's last byte
-  // are clamped to it (their bytes are never used). Caller images with an odd base or pitch take
-  // byte loads instead.
-  __shared__ int s_part[4][NPW][128];
-  __shared__ uint32_t s_win[4][NPW][11][11];
-  int* part = s_part[wave_id()][grp];
-  uint32_t(*win)[11] = s_win[wave_id()][grp];
-  int pl = 0, pr = 0;
-  const uint8_t* IL = nullptr;
-  const uint8_t* IR = nullptr;
-  if (ok) {
-    IL = level_img(b, g, il, levelL, &pl);
-    IR = level_img(b, g, ir, levelL, &pr);
+  // Every left keypoint's outputs have one writer: lane 0 of its group here when it has no
+  // candidate window, lane 10 after the SAD stage otherwise.
+  const int64_t o = (int64_t)f * g->kp_cap + iL;
+  if (valid && !ok && hl == 0) {
+    out.u_right[o] = -1.0f;
+    out.depth[o] = -1.0f;
+    ws.sad[o] = -1;
   }
-  const int al = (xcl - w) & ~3, ar = (xcr - L - w) & ~3;
-  const bool dw = ((((uintptr_t)IL | (uintptr_t)IR) | (uintptr_t)(pl | pr)) & 3) == 0;
-  const int lastw = (LG.w - 1) >> 2;
-  if (ok) {
+  if (!ok) return;  // whole groups leave: every DPP row below is full
+  // SAD of the 11 window offsets (level levelL, window centres (xcl, yc) and (xcr, yc)): lane
+  // r = 0..10 of the group owns window row yc - 5 + r and holds it in registers, 16 left bytes
+  // from column al = (xcl - 5) & ~3 and 28 right bytes from ar = (xcr - 10) & ~3 (lanes 11..15
+  // repeat row 10; their sums are not used). The loads go through buffer descriptors over the
+  // frame's two level-0 images and its two pyramids (wave-uniform, whatever levels the wave's four
+  // keypoints are on), so the lane offset is 32 bits and a read past the end of an image's last
+  // row returns zeros; no pair uses such a byte, nor one past the row's last pixel. Caller images
+  // whose base or pitch is no multiple of 4 are read byte by byte.
+  const LevelGeom& L0 = g->lv[0];
+  const uint8_t* const img_l = batch_image(b, il);
+  const uint8_t* const img_r = batch_image(b, ir);
+  const bool dw = ((((uintptr_t)img_l | (uintptr_t)img_r) | (uintptr_t)b.in_pitch) & 3) == 0;
+  // dword loads may read the dword that holds the row's last pixel, as the pyramid rows allow
+  const int bytes0 = __builtin_amdgcn_readfirstlane((L0.h - 1) * b.in_pitch +
+                                                    (dw ? (L0.w + 3) & ~3 : L0.w));
+  const int bytesp = __builtin_amdgcn_readfirstlane((int)g->pyr_bytes);
+  const __amdgpu_buffer_rsrc_t rs_l0 = buf_rsrc(img_l, bytes0), rs_r0 = buf_rsrc(img_r, bytes0);
+  const __amdgpu_buffer_rsrc_t rs_lp = buf_rsrc(b.pyr + (int64_t)il * g->pyr_bytes, bytesp);
+  const __amdgpu_buffer_rsrc_t rs_rp = buf_rsrc(b.pyr + (int64_t)ir * g->pyr_bytes, bytesp);
+  const int al = (xcl - 5) & ~3, ar = (xcr - 10) & ~3;
+  const int wy = yc - 5 + min(hl, 10);
+  uint32_t lw[4], rw[7];
+  auto rows = [&](__amdgpu_buffer_rsrc_t rl, __amdgpu_buffer_rsrc_t rr, int ol, int orr) {
+    const u32x4_t l4 = __builtin_amdgcn_raw_buffer_load_b128(rl, ol, 0, 0);
+    const u32x4_t r4 = __builtin_amdgcn_raw_buffer_load_b128(rr, orr, 0, 0);
+    const u32x3_t r3 = __builtin_amdgcn_raw_buffer_load_b96(rr, orr + 16, 0, 0);
 #pragma unroll
-    for (int rnd = 0; rnd < kRounds; rnd++) {
-      const int p = hl + G * rnd;
-      if (p < 121) {
-        const int r = p / 11, d = p - 11 * r;  // window row, dword slot (0-3 left, 4-10 right)
-        const bool left = d < 4;
-        const uint8_t* img = left ? IL : IR;
-        const int pitch = left ? pl : pr;
-        const int x0 = left ? al + 4 * d : ar + 4 * (d - 4);
-        const uint8_t* rowp = img + (int64_t)(yc - w + r) * pitch;
-        uint32_t v;
-        if (dw) {
-          v = reinterpret_cast<const uint32_t*>(rowp)[min(x0 >> 2, lastw)];
-        } else {
-          v = 0;
-          for (int j = 0; j < 4; j++)
-            v |= (uint32_t)rowp[min(x0 + j, LG.w - 1)] << (8 * j);
-        }
-        win[r][d] = v;
-      }
+    for (int i = 0; i < 4; i++) lw[i] = l4[i], rw[i] = r4[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) rw[4 + i] = r3[i];
+  };
+  if (levelL != 0) {
+    const int ro = (int)LG.offset + wy * LG.pitch;
+    rows(rs_lp, rs_rp, ro + al, ro + ar);
+  } else if (dw) {
+    const int ro = wy * b.in_pitch;
+    rows(rs_l0, rs_r0, ro + al, ro + ar);
+  } else {
+    const int ro = wy * b.in_pitch;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      lw[i] = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        lw[i] |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs_l0, ro + al + 4 * i + j, 0, 0)
+                 << (8 * j);
+    }
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+      rw[i] = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        rw[i] |= (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rs_r0, ro + ar + 4 * i + j, 0, 0)
+                 << (8 * j);
     }
   }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  const uint8_t* wb = reinterpret_cast<const uint8_t*>(&win[0][0]);  // row r at 44 r
-  if (ok) {
-    // A task (offset k, window row yr) sums |(IL - cl) - (IR - cr)| over 11 pixels as v_sad_u16
-    // on u16 pairs: (IL + 512) - (IR + 512 + cl - cr); v_perm builds each pair with the +512 bias
-    // bytes taken from a constant operand, and a 12th pair element is made equal on both sides.
-    const uint32_t* ww = &win[0][0];
-    const int oL = xcl - w - al, oR0 = xcr - L - w - ar;  // byte offsets of the rows (0..3)
-    const int cl = wb[44 * w + (xcl - al)];
-    constexpr uint32_t kBias = 0x02020202u;  // bias bytes: 0x0202 = 514 per u16 half
+  // Once per lane: the left row's 11 bytes from its window's first column (a), the right row's 21
+  // bytes from its first offset's first column (e), and from the centre row's lane (5) the dwords
+  // that hold the centre pixels cl = a[5] and cr_k = e[k + 5] (offset k's window is e[k..k+10]).
+  const uint32_t oL = (uint32_t)(xcl - 5 - al), oR = (uint32_t)(xcr - 10 - ar);
+  uint32_t a[3], e[6], ec[6];
 #pragma unroll
-    for (int rnd = 0; rnd < kRounds; rnd++) {
-      const int p = hl + G * rnd;
-      if (p < 121) {
-        const int k = p / 11, yr = p - 11 * k;  // offset k - L, window row yr - w
-        const int cr = wb[44 * w + 16 + (xcr + k - L - ar)];
-        const uint32_t* rowL = ww + 11 * yr;
-        const int oR = oR0 + k;  // 0..13: the right row's bytes oR .. oR + 10 (of 28)
-        const uint32_t* rowR = rowL + 4 + (oR >> 2);
-        const uint32_t l0 = rowL[0], l1 = rowL[1], l2 = rowL[2], l3 = rowL[3];
-        const uint32_t r0 = rowR[0], r1 = rowR[1], r2 = rowR[2], r3 = rowR[3];
-        const uint32_t a[3] = {__builtin_amdgcn_alignbyte(l1, l0, oL),
-                               __builtin_amdgcn_alignbyte(l2, l1, oL),
-                               __builtin_amdgcn_alignbyte(l3, l2, oL)};
-        const uint32_t bsh = (uint32_t)(oR & 3);
-        const uint32_t bb[3] = {__builtin_amdgcn_alignbyte(r1, r0, bsh),
-                                __builtin_amdgcn_alignbyte(r2, r1, bsh),
-                                __builtin_amdgcn_alignbyte(r3, r2, bsh)};
-        // cl - cr added to each u16 half (v_pk_add_u16 wraps per half; every sum lies in
-        // [257, 1022]): the last pair's high half stays the bias on both sides
-        typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
-        const unsigned short d = (unsigned short)(cl - cr);
-        const u16x2_t dd = {d, d}, dlast = {d, 0};
-        uint32_t acc = 0;
+  for (int i = 0; i < 3; i++) a[i] = __builtin_amdgcn_alignbyte(lw[i + 1], lw[i], oL);
 #pragma unroll
-        for (int j = 0; j < 6; j++) {
-          const uint32_t sel = j == 5 ? 0x04040402u : (j & 1) ? 0x04030402u : 0x05010400u;
-          const uint32_t A = __builtin_amdgcn_perm(kBias, a[j >> 1], sel);
-          const u16x2_t B = __builtin_bit_cast(u16x2_t, __builtin_amdgcn_perm(kBias, bb[j >> 1], sel)) +
-                            (j == 5 ? dlast : dd);
-          acc = __builtin_amdgcn_sad_u16(A, __builtin_bit_cast(uint32_t, B), acc);
-        }
-        part[p] = (int)acc;
-      }
-    }
+  for (int i = 0; i < 6; i++) e[i] = __builtin_amdgcn_alignbyte(rw[i + 1], rw[i], oR);
+  const uint32_t ac = __shfl(a[1], 5, G);
+#pragma unroll
+  for (int i = 0; i < 6; i++) ec[i] = i >= 1 && i <= 3 ? __shfl(e[i], 5, G) : 0u;
+  // A task (offset k, window row) sums |(IL - cl) - (IR - cr_k)| over 11 pixels as v_sad_u16 on
+  // u16 pairs: (IL + 512) against (IR + 512 + cl - cr_k); every half stays within [257, 1022].
+  // The left pairs are built once (v_perm takes the high byte 0x02 = +512 from a constant
+  // operand), the right pairs once per byte position (offsets k and k + 2 share all but one), and
+  // cl - cr_k + 512 is added per offset. The 12th element of a task is (cl + 512) against (cr_k +
+  // 512 + cl - cr_k): equal on both sides, from the same additions as the rest.
+  constexpr uint32_t kBias = 0x02020202u;  // a u16 half's high byte: + 512
+  constexpr uint32_t kBias2 = 0x02000200u;  // + 512 on both halves
+  uint32_t A[6];
+#pragma unroll
+  for (int j = 0; j < 5; j++)
+    A[j] = __builtin_amdgcn_perm(kBias, a[j >> 1], (j & 1) ? 0x04030402u : 0x05010400u);
+  A[5] = __builtin_amdgcn_perm(ac, a[2], 0x0c050c02u) + kBias2;          // (a[10], cl) + 512
+  const uint32_t C = __builtin_amdgcn_perm(0u, ac, 0x0c010c01u) + kBias2;  // (cl, cl) + 512
+  int S[11];
+#pragma unroll
+  for (int k = 0; k < 11; k++) {
+    const int c = k + 5, hc = c & 3, p = k + 10, h = p & 3;  // centre and last byte of offset k
+    const uint32_t crr =
+        __builtin_amdgcn_perm(0u, ec[c >> 2], 0x0c000c00u | (uint32_t)hc | (uint32_t)hc << 16);
+    const uint32_t dd = C - crr;  // (cl + 512 - cr_k) in both halves, each positive: no borrow
+    uint32_t acc = 0;
+#pragma unroll
+    for (int j = 0; j < 5; j++)
+      acc = __builtin_amdgcn_sad_u16(A[j], byte_pair(e, k + 2 * j) + dd, acc);
+    const uint32_t last = __builtin_amdgcn_perm(
+        ec[c >> 2], e[p >> 2], 0x0c000c00u | (uint32_t)h | (uint32_t)(4 + hc) << 16);  // (e[p], cr_k)
+    S[k] = (int)__builtin_amdgcn_sad_u16(A[5], last + dd, acc);
   }
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  int sad = 0x7fffffff;
-  if (ok && hl < 2 * L + 1) {
-    int acc = 0;
+  // rows summed per offset down the DPP row: lane 10 ends with rows 0..10
 #pragma unroll
-    for (int yy = 0; yy < 2 * w + 1; yy++) acc += part[11 * hl + yy];
-    sad = acc;
+  for (int k = 0; k < 11; k++) {
+    S[k] += __builtin_amdgcn_update_dpp(0, S[k], 0x111, 0xf, 0xf, true);  // row_shr:1
+    S[k] += __builtin_amdgcn_update_dpp(0, S[k], 0x112, 0xf, 0xf, true);  // row_shr:2
+    S[k] += __builtin_amdgcn_update_dpp(0, S[k], 0x114, 0xf, 0xf, true);  // row_shr:4
+    S[k] += __builtin_amdgcn_update_dpp(0, S[k], 0x118, 0xf, 0xf, true);  // row_shr:8
   }
+  if (hl != 10) return;
   float vDists[11];
 #pragma unroll
-  for (int k = 0; k < 11; k++) vDists[k] = (float)__shfl(sad, G * grp + k, 64);
-  if (!ok || hl != 0) return;
+  for (int k = 0; k < 11; k++) vDists[k] = (float)S[k];
   int bestSad = 0x7fffffff, bestincR = 0;
 #pragma unroll
   for (int k = 0; k < 11; k++) {
@@ -410,23 +423,30 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(ImageBatch b,
       bestincR = k - L;
     }
   }
-  if (bestincR == -L || bestincR == L) return;
-  const float dist1 = vDists[L + bestincR - 1];
-  const float dist2 = vDists[L + bestincR];
-  const float dist3 = vDists[L + bestincR + 1];
-  const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
-  if (deltaR < -1 || deltaR > 1) return;
-  float bestuR = LG.scale * ((float)scaleduR0 + (float)bestincR + deltaR);
-  float disparity = (uL - bestuR);
-  if (disparity >= minD && disparity < maxD) {
-    if (disparity <= 0) {
-      disparity = 0.01f;
-      bestuR = uL - 0.01f;
+  float o_ur = -1.0f, o_depth = -1.0f;
+  int o_sad = -1;
+  if (!(bestincR == -L || bestincR == L)) {
+    const float dist1 = vDists[L + bestincR - 1];
+    const float dist2 = vDists[L + bestincR];
+    const float dist3 = vDists[L + bestincR + 1];
+    const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
+    if (!(deltaR < -1 || deltaR > 1)) {
+      float bestuR = LG.scale * ((float)xcr + (float)bestincR + deltaR);
+      float disparity = (uL - bestuR);
+      if (disparity >= minD && disparity < maxD) {
+        if (disparity <= 0) {
+          disparity = 0.01f;
+          bestuR = uL - 0.01f;
+        }
+        o_depth = cam.bf / disparity;
+        o_ur = bestuR;
+        o_sad = bestSad;
+      }
     }
-    out.depth[o] = cam.bf / disparity;
-    out.u_right[o] = bestuR;
-    ws.sad[o] = bestSad;
   }
+  out.u_right[o] = o_ur;
+  out.depth[o] = o_depth;
+  ws.sad[o] = o_sad;
 }
 
 // Median SAD filter (:564-576): drop matches whose SAD >= 2.1 * median. The median (element
@@ -618,7 +638,7 @@ void launch_stereo(const ImageBatch& b, const OrbGeomDev& gd, const Camera& cam,
   else
     SLAMGPU_LAUNCH("stereo_rows", st, stereo_rows_kernel<256>, dim3(n_frames), dim3(256), 0, st,
                    gd.dev, ext, nrows, ws, gd.ws.err);
-  constexpr int kG = STEREO_LANES, kPerBlock = 4 * (64 / kG);
+  constexpr int kG = 16, kPerBlock = 4 * (64 / kG);
   SLAMGPU_LAUNCH("stereo_match", st, stereo_match_kernel<kG>,
                  dim3((g.kp_cap + kPerBlock - 1) / kPerBlock, n_frames), dim3(256), 0, st, b,
                  gd.dev, ext, cam, nrows, ws, out);

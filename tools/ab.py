@@ -1,6 +1,6 @@
 """A/B timing of library builds: python tools/ab.py tools/abl/libslamgpu_a.so ... [-- bench args]
 Runs bench.py once per build (SLAMGPU_LIB), each under its own time limit, and prints the step
-time, throughput and per-kernel ms. Stops at the first failing run."""
+time, throughput and per-kernel ms (in the step / alone). Stops at the first failing run."""
 import json
 import os
 import subprocess
@@ -21,6 +21,9 @@ for lib in argv:
         sys.exit(1)
     d = json.loads(p.stdout.strip().splitlines()[-1])
     k = d.get("kernel_ms_per_step", {})
-    ks = " ".join(f"{n}={v:.3f}" for n, v in k.items() if v > 0.02)
+    alone = {n: e.get("alone_ms_per_step") for n, e in d.get("kernels_standalone", {}).items()}
+    # kernel=ms in the step/ms alone (--full: kernels_standalone)
+    ks = " ".join(f"{n}={v:.3f}" + (f"/{alone[n]:.3f}" if alone.get(n) else "")
+                  for n, v in k.items() if v > 0.02)
     print(f"{os.path.basename(lib):28s} {d['ms_per_step']:.3f} ms {d['value']:.0f} f/s | {ks}",
           flush=True)
