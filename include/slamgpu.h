@@ -5,7 +5,7 @@
  *   ORBextractor            src/orb_features/orb_extractor.h:25-93
  *   Frame stereo matching   src/data/frame.cpp:406-577 (ComputeStereoMatches), grid :234-248
  *   OrbMatcher              src/orb_features/orb_matcher.h:14-119 (DescriptorDistance and the
- *                           two per-frame SearchByProjection overloads)
+ *                           three per-frame SearchByProjection overloads)
  * POD types and caller-owned buffers only; every function returns 0 on success or a negative
  * SLAMGPU_E* code, with a message in slamgpu_last_error(). One context owns one HIP device,
  * one stream and all device workspaces; functions on different contexts may run concurrently
@@ -249,6 +249,54 @@ int slamgpu_search_by_projection_mps_device(slamgpu_ctx* ctx, const slamgpu_mps_
                                             int64_t mp_stride, int* d_nmatches, int n_frames,
                                             void* stream);
 
+/* A map point of the relocalisation candidate keyframe for SearchByProjection(CurrentFrame, pKF,
+ * sAlreadyFound, th, ORBdist) (orb_matcher.cpp:1455-1582): pKF->GetMapPointMatches() in keypoint
+ * order. 64 bytes. */
+typedef struct {
+  float xyz[3];       /* MapPoint::GetWorldPos()                                              */
+  float max_dist;     /* max_dist_ and min_dist_ as stored: Get{Max,Min}DistanceInvariance's   */
+  float min_dist;     /* 1.2 / 0.8 factors are applied inside                                  */
+  float kf_angle;     /* pKF->undistorted_keypoints[i].angle                                   */
+  int32_t mp_id;      /* caller's identity of the map point (>= 0), written into map_point     */
+  int32_t skip;       /* the slot is null, isBad() or in sAlreadyFound (the snapshot at entry) */
+  uint8_t desc[32];   /* MapPoint::GetDescriptor()                                             */
+} slamgpu_reloc_query;
+
+typedef struct {
+  float Rcw[9];       /* CurrentFrame pose rotation, row major                                 */
+  float tcw[3];
+  float Ow[3];        /* -Rcw.t() * tcw as the caller's cv::Mat arithmetic rounds it           */
+  float th;           /* window factor (10, then 3: tracker.cpp:940, :958)                     */
+  int32_t orb_dist;   /* ORBdist in [0, 256]: accepted iff bestDist <= orb_dist (100, then 64) */
+  int32_t check_ori;  /* mbCheckOrientation                                                    */
+} slamgpu_reloc_pose; /* 72 bytes */
+
+/* Host call on frame `frame` of the last frontend/frame call, as the two calls above. n must be
+ * the frame's keypoint count. map_point[n] is in/out; blocked[n] here means "slot i holds a map
+ * point" (CurrentFrame.GetMapPoint(i) != nullptr): it is derived from map_point >= 0 at entry and
+ * returned consistent with map_point. There is no depth gate (a point behind the camera that
+ * projects inside the image bounds is searched), no right-coordinate gate and no ratio test; the
+ * octave window is level-1 .. level+1; every accepted query occupies its slot. A query whose
+ * invzc, u, v, dist3D or max_dist / dist3D is not finite, or whose ratio is <= 0 (undefined
+ * behaviour in the reference), matches nothing. Errors (SLAMGPU_EINVAL, nothing written): a null
+ * pointer, frame out of range, n different from the frame's keypoint count, orb_dist outside
+ * [0, 256], a non-finite th. */
+int slamgpu_search_by_projection_reloc(slamgpu_ctx* ctx, int frame,
+                                       const slamgpu_reloc_query* queries, int n_queries,
+                                       const slamgpu_reloc_pose* pose, int32_t* map_point,
+                                       uint8_t* blocked, int n, int* nmatches);
+/* Batched over the frames of the last frontend call, one pose per frame, as the *_device calls
+ * above; d_blocked[f][i] != 0 = "slot i of frame f holds a map point" is the caller's at entry.
+ * Never allocates and never synchronises: total_queries beyond max_frames * kp_cap (the
+ * workspace the context is created with) is SLAMGPU_ECAP. Poses are read on the device, so
+ * orb_dist / th are the caller's to keep in range. */
+int slamgpu_search_by_projection_reloc_device(slamgpu_ctx* ctx, const slamgpu_reloc_query* d_queries,
+                                              int total_queries, const int* d_q_start, const int* d_q_count,
+                                              int max_queries, const slamgpu_reloc_pose* d_poses,
+                                              int32_t* d_map_point, uint8_t* d_blocked,
+                                              int64_t mp_stride, int* d_nmatches, int n_frames,
+                                              void* stream);
+
 /* Builds frame-to-frame queries on the device from the last frontend call: for frame f >= 1,
  * every left keypoint of frame f-1 with stereo depth becomes a map point at
  * Frame::UnprojectStereo(i) (frame.cpp:594-607) under d_poses[f-1] -- the visual-odometry points
@@ -281,5 +329,8 @@ int slamgpu_trace_marker(int id, void* stream);
 
 #ifdef __cplusplus
 }
+static_assert(sizeof(slamgpu_reloc_query) == 64, "slamgpu_reloc_query is 64 bytes");
+static_assert(sizeof(slamgpu_reloc_pose) == 72 && sizeof(slamgpu_reloc_pose) % 8 == 0,
+              "slamgpu_reloc_pose is 72 bytes");
 #endif
 #endif /* SLAMGPU_H_ */

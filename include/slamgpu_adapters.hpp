@@ -1566,4 +1566,196 @@ inline int search_by_sim3(int kf1_index, int kf2_index, const KeyFrameView* kfs,
   return nfound;
 }
 
+// ---- OrbMatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>&
+// sAlreadyFound, th, ORBdist) (orb_matcher.cpp:1455-1582), Tracker::Relocalization
+// (tracker.cpp:938-960: (10, 100), then (3, 64)). Runs on the frame the context holds.
+
+struct RelocInput {
+  std::vector<slamgpu_reloc_query> queries;  // one per keyframe keypoint, keypoint order
+  slamgpu_reloc_pose pose;
+};
+
+// Ow = -Rcw.t() * tcw (:1461) for callers without their own cv::Mat arithmetic: the products and
+// their sum in double, rounded to float once. The library itself takes Ow as given
+// (slamgpu_reloc_pose): a caller with OpenCV passes what its own expression gave.
+inline void reloc_camera_center(const float* Tcw, float* Ow) {
+  for (int k = 0; k < 3; ++k) {
+    double s = 0.0;
+    for (int r = 0; r < 3; ++r) s += (double)Tcw[4 * r + k] * (double)Tcw[4 * r + 3];
+    Ow[k] = (float)-s;
+  }
+}
+
+// pKF->GetMapPointMatches() in keypoint order (:1469-1477): a slot that is null, bad or in
+// already_found (map point indices: sAlreadyFound at entry) becomes a skip record. mp_id is the
+// map point's index, so the frame's map point array is the call's map_point argument as it is.
+inline RelocInput gather_search_by_projection_reloc(const FrameView& current, const KeyFrameView& kf,
+                                                    const MapPointView* mps,
+                                                    const MapPointGeometry* geom,
+                                                    const int32_t* already_found, int n_found,
+                                                    const float* Ow, float th, int orb_dist,
+                                                    bool check_ori) {
+  RelocInput in;
+  in.queries.resize(kf.n_kps > 0 ? kf.n_kps : 0);
+  std::vector<int32_t> found(already_found, already_found + n_found);
+  std::sort(found.begin(), found.end());
+  for (int i = 0; i < kf.n_kps; ++i) {
+    slamgpu_reloc_query& q = in.queries[i];
+    std::memset(&q, 0, sizeof q);
+    const int m = kf.map_points[i];
+    q.skip = m < 0 || mps[m].bad || std::binary_search(found.begin(), found.end(), m);
+    if (q.skip) continue;
+    std::memcpy(q.xyz, mps[m].xyz, sizeof q.xyz);
+    q.max_dist = geom[m].max_dist;
+    q.min_dist = geom[m].min_dist;
+    q.kf_angle = kf.undist_kps[i].angle;
+    q.mp_id = m;
+    std::memcpy(q.desc, mps[m].desc, 32);
+  }
+  slamgpu_reloc_pose& p = in.pose;
+  std::memset(&p, 0, sizeof p);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) p.Rcw[3 * r + c] = current.Tcw[4 * r + c];
+    p.tcw[r] = current.Tcw[4 * r + 3];
+    p.Ow[r] = Ow[r];
+  }
+  p.th = th;
+  p.orb_dist = orb_dist;
+  p.check_ori = check_ori ? 1 : 0;
+  return in;
+}
+
+// CurrentFrame.SetMapPoint(bestIdx2, pMP) / SetMapPoint(idx, nullptr) (:1543, :1574): the slots
+// the call returns are map point indices already (mp_id = index); copies them into the frame's
+// array and returns how many slots hold a point now that did not at entry.
+inline int apply_search_by_projection_reloc(const int32_t* slot, int32_t* current_map_points, int n) {
+  int assigned = 0;
+  for (int i = 0; i < n; ++i) {
+    if (slot[i] >= 0 && current_map_points[i] < 0) ++assigned;
+    current_map_points[i] = slot[i];
+  }
+  return assigned;
+}
+
+// The whole call on frame `frame` of the context's last frame / frontend call; current_map_points
+// (the frame's map point index per keypoint, -1 = none) is in/out. Returns nmatches; throws on a
+// device error.
+inline int search_by_projection_reloc(slamgpu_ctx* ctx, int frame, const FrameView& current,
+                                      const KeyFrameView& kf, const MapPointView* mps,
+                                      const MapPointGeometry* geom, const int32_t* already_found,
+                                      int n_found, const float* Ow, float th, int orb_dist,
+                                      bool check_ori, int32_t* current_map_points,
+                                      slamgpu_reloc_pose* pose_used = nullptr) {
+  const RelocInput in = gather_search_by_projection_reloc(current, kf, mps, geom, already_found,
+                                                          n_found, Ow, th, orb_dist, check_ori);
+  if (pose_used) *pose_used = in.pose;
+  std::vector<int32_t> slot(current_map_points, current_map_points + current.n_kps);
+  std::vector<uint8_t> blocked(current.n_kps > 0 ? current.n_kps : 1);
+  int nm = 0;
+  const int rc = slamgpu_search_by_projection_reloc(ctx, frame, in.queries.data(),
+                                                    (int)in.queries.size(), &in.pose, slot.data(),
+                                                    blocked.data(), current.n_kps, &nm);
+  if (rc != SLAMGPU_OK) throw std::runtime_error(std::string("slamgpu: ") + slamgpu_last_error(ctx));
+  apply_search_by_projection_reloc(slot.data(), current_map_points, current.n_kps);
+  return nm;
+}
+
+// One step of relocalization_refine as it ran, for tests and logs.
+struct RelocRefineStep {
+  enum Kind : int32_t { kPoseOptimization = 0, kSearch = 1 };
+  int32_t kind;
+  int32_t result;                      // nGood of the optimization / nadditional of the search
+  float Tcw_in[16], Tcw_out[16];
+  slamgpu_reloc_pose pose;             // the search's pose record (zero for an optimization)
+  std::vector<int32_t> found;          // the search's sAlreadyFound
+  std::vector<int32_t> map_points_in;  // the frame's slots before the step ...
+  std::vector<int32_t> map_points_out; // ... and after it (outliers not yet cleared)
+  std::vector<uint8_t> outlier_out;    // the frame's outlier flags after the step
+};
+
+// Tracker::Relocalization's refinement of one candidate (tracker.cpp:924-975), after the PnP
+// inliers were set as the frame's map points and sFound (:915-922): PoseOptimization; with fewer
+// than 10 inliers the candidate is dropped; outliers cleared; with fewer than 50 the (10, 100)
+// search and, if that brings the count to 50, PoseOptimization; with 30 < nGood < 50 sFound
+// rebuilt from the frame's slots, the (3, 64) search and, if that brings the count to 50, the
+// final PoseOptimization and clearing. Tcw[16], map_points[n] and outlier[n] of `current` are
+// updated in place through the three mutable pointers (current.Tcw / .map_points / .outlier must
+// point at the same arrays). Returns nGood: the caller accepts the candidate iff nGood >= 50.
+inline int relocalization_refine(slamgpu_ctx* ctx, int frame, const slamgpu_camera& cam,
+                                 const float* inv_sigma2, int nlevels, const FrameView& current,
+                                 float* Tcw, int32_t* map_points, uint8_t* outlier,
+                                 const KeyFrameView& kf, const MapPointView* mps,
+                                 const MapPointGeometry* geom, std::vector<int32_t> found,
+                                 bool check_ori, std::vector<RelocRefineStep>* trace = nullptr,
+                                 const std::function<void(const float*, float*)>& center =
+                                     reloc_camera_center) {
+  if (current.Tcw != Tcw || current.map_points != map_points || current.outlier != outlier)
+    throw std::invalid_argument("relocalization_refine: `current` must view the mutable arrays");
+  const int n = current.n_kps;
+  auto begin_step = [&](int kind) {
+    RelocRefineStep s;
+    s.kind = kind;
+    s.result = 0;
+    std::memcpy(s.Tcw_in, Tcw, sizeof s.Tcw_in);
+    std::memset(&s.pose, 0, sizeof s.pose);
+    s.map_points_in.assign(map_points, map_points + n);
+    return s;
+  };
+  auto end_step = [&](RelocRefineStep& s, int result) {
+    s.result = result;
+    std::memcpy(s.Tcw_out, Tcw, sizeof s.Tcw_out);
+    s.map_points_out.assign(map_points, map_points + n);
+    s.outlier_out.assign(outlier, outlier + n);
+    if (trace) trace->push_back(std::move(s));
+  };
+  auto pose_optimization = [&]() {
+    RelocRefineStep s = begin_step(RelocRefineStep::kPoseOptimization);
+    const PoseGraph g = gather_pose_optimization(current, mps);
+    std::vector<uint8_t> edge_outlier(g.edges.size() + 1, 0);
+    int n_inliers = 0;
+    if (slamgpu_pose_optimization(&cam, inv_sigma2, nlevels, g.edges.data(), (int)g.edges.size(),
+                                  Tcw, edge_outlier.data(), &n_inliers) != SLAMGPU_OK)
+      throw std::runtime_error(std::string("slamgpu: ") + slamgpu_optimizer_last_error());
+    apply_pose_optimization(g, edge_outlier.data(), outlier);
+    end_step(s, n_inliers);
+    return n_inliers;
+  };
+  auto clear_outliers = [&]() {
+    for (int io = 0; io < n; ++io)
+      if (outlier[io]) map_points[io] = -1;
+  };
+  auto search = [&](float th, int orb_dist) {
+    RelocRefineStep s = begin_step(RelocRefineStep::kSearch);
+    s.found = found;
+    float Ow[3];
+    center(Tcw, Ow);
+    const int nm = search_by_projection_reloc(ctx, frame, current, kf, mps, geom, found.data(),
+                                              (int)found.size(), Ow, th, orb_dist, check_ori,
+                                              map_points, &s.pose);
+    end_step(s, nm);
+    return nm;
+  };
+
+  int nGood = pose_optimization();
+  if (nGood < 10) return nGood;
+  clear_outliers();
+  if (nGood < 50) {
+    int nadditional = search(10.0f, 100);
+    if (nadditional + nGood >= 50) {
+      nGood = pose_optimization();
+      if (nGood > 30 && nGood < 50) {
+        found.clear();
+        for (int ip = 0; ip < n; ++ip)
+          if (map_points[ip] >= 0) found.push_back(map_points[ip]);
+        nadditional = search(3.0f, 64);
+        if (nGood + nadditional >= 50) {
+          nGood = pose_optimization();
+          clear_outliers();
+        }
+      }
+    }
+  }
+  return nGood;
+}
+
 }  // namespace slamgpu_adapter

@@ -42,6 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_host_stage_check()
         build_sim3solver_adapter_check()
         build_pnpsolver_adapter_check()
+        build_reloc_adapter_check()
         build_device_math_check()
         return LIB
     objdir = os.path.join(PKG, "build")
@@ -73,6 +74,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_host_stage_check()
     build_sim3solver_adapter_check()
     build_pnpsolver_adapter_check()
+    build_reloc_adapter_check()
     build_device_math_check()
     return LIB
 
@@ -152,6 +154,25 @@ def build_pnpsolver_adapter_check() -> str:
                     "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", PNPSOLVER_ADAPTER_BIN],
                    check=True)
     return PNPSOLVER_ADAPTER_BIN
+
+
+RELOC_ADAPTER_SRC = os.path.join(ROOT, "tests", "reloc_adapter_check.cpp")
+RELOC_ADAPTER_BIN = os.path.join(ROOT, "tests", "reloc_adapter_check")
+
+
+def build_reloc_adapter_check() -> str:
+    """g++ build of tests/reloc_adapter_check.cpp: relocalization_refine of
+    include/slamgpu_adapters.hpp (PoseOptimization and the two relocalisation searches of
+    tracker.cpp:924-975 on the frame the context holds) driven from C++ against libslamgpu.so."""
+    deps = [RELOC_ADAPTER_SRC, LIB] + glob.glob(os.path.join(ROOT, "include", "*.h*"))
+    if os.path.exists(RELOC_ADAPTER_BIN) and os.path.getmtime(RELOC_ADAPTER_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return RELOC_ADAPTER_BIN
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I",
+                    os.path.join(ROOT, "include"), RELOC_ADAPTER_SRC, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", RELOC_ADAPTER_BIN],
+                   check=True)
+    return RELOC_ADAPTER_BIN
 
 
 GEOMETRY_SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")

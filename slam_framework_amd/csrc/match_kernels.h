@@ -107,6 +107,29 @@ struct MpsQuery {
 static_assert(sizeof(MpsQuery) == 80, "MpsQuery layout");
 static_assert(sizeof(F2FPose) == 72, "F2FPose layout");
 
+// One query of SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)
+// (orb_matcher.cpp:1455-1582): a map point of the relocalisation candidate keyframe.
+struct RelocQuery {
+  float xyz[3];        // MapPoint::GetWorldPos
+  float max_dist;      // max_dist_ / min_dist_ (the 1.2 / 0.8 factors are applied on the device)
+  float min_dist;
+  float kf_angle;      // pKF->undistorted_keypoints[i].angle
+  int mp_id;
+  int skip;            // null slot, isBad() or in sAlreadyFound
+  uint8_t desc[32];
+};
+static_assert(sizeof(RelocQuery) == 64, "RelocQuery layout");
+
+struct RelocPose {
+  float Rcw[9];        // current frame, row major
+  float tcw[3];
+  float Ow[3];         // -Rcw.t() * tcw, the caller's
+  float th;
+  int orb_dist;        // ORBdist: accepted iff bestDist <= orb_dist
+  int check_ori;
+};
+static_assert(sizeof(RelocPose) == 72, "RelocPose layout");
+
 struct MatchWorkspace {
   uint64_t* topk;      // [query][kTopK] (dist, grid order) keys
   int* ncand;          // [query]
@@ -119,6 +142,7 @@ struct MatchIO {
   const int* q_count;  // [frame]
   int* map_point;      // [frame][kp_cap] in/out: map point id per keypoint (-1 none)
   uint8_t* blocked;    // [frame][kp_cap] in/out: slot holds a map point with observations
+                       // (relocalisation search: slot holds a map point)
   int* nmatches;       // [frame]
   int64_t mp_stride;   // stride of map_point/blocked between frames (keypoints)
 };
@@ -143,6 +167,12 @@ void launch_search_mps(const FrameKps& cur, const float* u_right, int64_t ur_str
                        float nnratio, int th, int n_frames, int max_queries_per_frame,
                        const GridWorkspace& gw, const MatchWorkspace& mw, const MatchIO& io,
                        hipStream_t st);
+
+void launch_search_reloc(const FrameKps& cur, const float* u_right, int64_t ur_stride,
+                         const Camera& cam, const OrbGeomDev& g, const RelocQuery* queries,
+                         const RelocPose* poses, int n_frames, int max_queries_per_frame,
+                         const GridWorkspace& gw, const MatchWorkspace& mw, const MatchIO& io,
+                         hipStream_t st);
 
 // Queries for frame f from frame f-1's stereo keypoints (frame 0 gets none); queries of frame f
 // occupy queries[f * kp_cap ...].

@@ -6,13 +6,17 @@
 //   grid_build      64x48 keypoint grid (CSR)         Frame::AssignFeaturesToGrid :234-248
 //   search_cand     projection + window + Hamming     OrbMatcher::SearchByProjection (both
 //   search_resolve  greedy in-order claims            overloads, orb_matcher.cpp:13-103 and
-//                                                     :1312-1453) + rotation histogram
+//                                                     :1312-1453) + rotation histogram; and the
+//                                                     relocalisation overload (Frame, KeyFrame,
+//                                                     sAlreadyFound, th, ORBdist) :1455-1582
 // Every Hamming distance is popcount(a ^ b) over 4 x u64 (== DescriptorDistance, :1630-1646).
 // The projection matchers are greedy in query order (a keypoint taken by an earlier query whose
 // map point has observations is skipped, :59-63 / :1389-1393), so candidate search is parallel
 // over queries and only a short claim-resolution pass per frame is sequential.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "device_math.h"
 #include "timing.h"
@@ -1074,6 +1078,61 @@ __device__ bool mps_ctx(const MpsQuery& q, int th, const OrbGeom* g, ScanCtx* c)
   return true;
 }
 
+// cv::norm of a 3-vector: a double sum of squares, its sqrt rounded to float.
+__device__ __forceinline__ float norm3(float a, float b, float c) {
+  double s = 0.0;
+  s += (double)a * (double)a;
+  s += (double)b * (double)b;
+  s += (double)c * (double)c;
+  return (float)sqrt(s);
+}
+
+// SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) per-query setup
+// (orb_matcher.cpp:1473-1513; PredictScale map_point.cpp:382-396). No depth gate and no
+// right-coordinate gate; the octave window is level-1 .. level+1. Where the reference's
+// arithmetic is undefined (a non-finite invzc, u, v, dist3D or max_dist / dist3D, a ratio <= 0:
+// float -> int of NaN / inf in GetFeaturesInArea or PredictScale) the query matches nothing.
+__device__ bool reloc_ctx(const RelocQuery& q, const RelocPose& P, const Camera& cam,
+                          const OrbGeom* g, ScanCtx* c) {
+  if (q.skip) return false;
+  const float xc = mat3_row(P.Rcw, 0, q.xyz, P.tcw[0]);
+  const float yc = mat3_row(P.Rcw, 1, q.xyz, P.tcw[1]);
+  const float zc = mat3_row(P.Rcw, 2, q.xyz, P.tcw[2]);
+  const float invzc = (float)(1.0 / (double)zc);
+  const float u = fmaf(cam.fx * xc, invzc, cam.cx);
+  const float v = fmaf(cam.fy * yc, invzc, cam.cy);
+  if (!isfinite(invzc) || !isfinite(u) || !isfinite(v)) return false;
+  if (u < cam.min_x || u > cam.max_x) return false;
+  if (v < cam.min_y || v > cam.max_y) return false;
+  const float dist3D = norm3(q.xyz[0] - P.Ow[0], q.xyz[1] - P.Ow[1], q.xyz[2] - P.Ow[2]);
+  if (!isfinite(dist3D)) return false;
+  if (dist3D < 0.8f * q.min_dist || dist3D > 1.2f * q.max_dist) return false;
+  const float ratio = q.max_dist / dist3D;
+  if (!isfinite(ratio) || !(ratio > 0.0f)) return false;
+  int level = (int)ceilf(glibc_logf(ratio) / g->log_scale_factor);
+  level = level < 0 ? 0 : (level >= g->nlevels ? g->nlevels - 1 : level);
+  c->x = u;
+  c->y = v;
+  c->r = P.th * g->lv[level].scale;
+  c->min_level = level - 1;
+  c->max_level = level + 1;
+  c->ur = 0.0f;
+  c->gate = __builtin_huge_valf();  // no right-coordinate gate
+  c->max_dist = P.orb_dist;  // a best above ORBdist never claims
+  c->desc = q.desc;
+  return true;
+}
+
+// The per-frame pose record of a query type (the local-map search has none).
+template <typename Q>
+struct SearchPose {
+  using type = F2FPose;
+};
+template <>
+struct SearchPose<RelocQuery> {
+  using type = RelocPose;
+};
+
 #ifndef SEARCH_LANES
 #define SEARCH_LANES 16
 #endif
@@ -1081,8 +1140,9 @@ constexpr int kSearchG = SEARCH_LANES;  // lanes per query in search_cand (16 or
 template <typename Q>
 __global__ __launch_bounds__(256) void search_cand_kernel(
     FrameKps cur, const float* __restrict__ u_right, int64_t ur_stride, Camera cam,
-    const OrbGeom* __restrict__ g, const Q* __restrict__ queries, const F2FPose* __restrict__ poses,
-    int th, GridWorkspace gw, MatchWorkspace mw, MatchIO io) {
+    const OrbGeom* __restrict__ g, const Q* __restrict__ queries,
+    const typename SearchPose<Q>::type* __restrict__ poses, int th, GridWorkspace gw,
+    MatchWorkspace mw, MatchIO io) {
   int f, bx;
   xcd_image_block(&f, &bx);  // a frame's work-groups share one XCD's L2 (its grid and keypoints)
   // kSearchG lanes per query: 64 / kSearchG queries per wave
@@ -1101,8 +1161,10 @@ __global__ __launch_bounds__(256) void search_cand_kernel(
   F.blocked = io.blocked + f * io.mp_stride;
   ScanCtx c;
   bool ok;
-  if constexpr (sizeof(Q) == sizeof(F2FQuery)) {
+  if constexpr (std::is_same<Q, F2FQuery>::value) {
     ok = f2f_ctx(queries[q], poses[f], cam, g, &c);
+  } else if constexpr (std::is_same<Q, RelocQuery>::value) {
+    ok = reloc_ctx(queries[q], poses[f], cam, g, &c);
   } else {
     ok = mps_ctx(queries[q], th, g, &c);
   }
@@ -1130,9 +1192,15 @@ constexpr int kResolveLdsQ = 4096;
 template <typename Q>
 __global__ __launch_bounds__(64) void search_resolve_kernel(
     FrameKps cur, const float* __restrict__ u_right, int64_t ur_stride, Camera cam,
-    const OrbGeom* __restrict__ g, const Q* __restrict__ queries, const F2FPose* __restrict__ poses,
-    int th, float nnratio, GridWorkspace gw, MatchWorkspace mw, MatchIO io) {
-  constexpr bool kF2F = sizeof(Q) == sizeof(F2FQuery);
+    const OrbGeom* __restrict__ g, const Q* __restrict__ queries,
+    const typename SearchPose<Q>::type* __restrict__ poses, int th, float nnratio,
+    GridWorkspace gw, MatchWorkspace mw, MatchIO io) {
+  // kReloc: the relocalisation overload resolves as the frame-to-frame one does (distance gate,
+  // rotation histogram), with every query blocking and the caller's ORBdist as the gate -- its
+  // kept candidates are all <= ORBdist (reloc_ctx), so any kept candidate is accepted
+  constexpr bool kReloc = std::is_same<Q, RelocQuery>::value;
+  constexpr bool kF2F = std::is_same<Q, F2FQuery>::value || kReloc;
+  constexpr int kAccept = kReloc ? 256 : TH_HIGH;
   __shared__ uint32_t claimed[128];  // kp_cap <= 4096
   __shared__ int hist[HISTO_LENGTH];
   __shared__ float s_kang[kF2F ? 4096 : 1];
@@ -1213,9 +1281,14 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
       for (int k = 0; k < kTopK; k++) in.key[k] = mw.topk[(int64_t)q * kTopK + k];
       in.nc = mw.ncand[q];
       const Q& qq = queries[q];
-      in.mpw = (qq.mp_id & 0x7fffffff) | (qq.blocks ? (int)0x80000000u : 0);
       in.qang = 0.f;
-      if constexpr (kF2F) in.qang = qq.last_angle;
+      if constexpr (kReloc) {
+        in.mpw = (qq.mp_id & 0x7fffffff) | (int)0x80000000u;  // SetMapPoint: every accept blocks
+        in.qang = qq.kf_angle;
+      } else {
+        in.mpw = (qq.mp_id & 0x7fffffff) | (qq.blocks ? (int)0x80000000u : 0);
+        if constexpr (kF2F) in.qang = qq.last_angle;
+      }
     } else {
 #pragma unroll
       for (int k = 0; k < kTopK; k++) in.key[k] = kNoKey;
@@ -1274,7 +1347,7 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
           navail++;
         }
         // accepted blocking choice -> owner (the lowest such lane wins the keypoint)
-        bool acc = b1 != kNoKey && key_dist(b1) <= TH_HIGH;
+        bool acc = b1 != kNoKey && key_dist(b1) <= kAccept;
         if constexpr (!kF2F) {
           if (acc) {
             const int lv1 = s_koct[key_idx(b1)];
@@ -1302,7 +1375,7 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
       auto commit = [&](bool doit, uint64_t c1, uint64_t c2) {
         // acceptance (F2F: distance gate; local map: + ratio test, :76-99)
         const bool touched = doit && c1 != kNoKey;
-        bool acc = touched && key_dist(c1) <= TH_HIGH;
+        bool acc = touched && key_dist(c1) <= kAccept;
         if constexpr (!kF2F) {
           if (acc) {
             const int lv1 = s_koct[key_idx(c1)];
@@ -1348,7 +1421,8 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
         ScanCtx c;
         bool okc;
         const int qr = q0 + c0 + r;
-        if constexpr (kF2F) okc = f2f_ctx(queries[qr], poses[f], cam, g, &c);
+        if constexpr (kReloc) okc = reloc_ctx(queries[qr], poses[f], cam, g, &c);
+        else if constexpr (kF2F) okc = f2f_ctx(queries[qr], poses[f], cam, g, &c);
         else okc = mps_ctx(queries[qr], th, g, &c);
         uint64_t top[kTopK];
         if (okc) scan_query(c, cam, F, claimed, top, lane, g->kp_cap);
@@ -1428,6 +1502,18 @@ void launch_search_mps(const FrameKps& cur, const float* u_right, int64_t ur_str
   SLAMGPU_LAUNCH("search_resolve", st, search_resolve_kernel<MpsQuery>, dim3(n_frames), dim3(64), 0, st, cur,
                      u_right, ur_stride, cam, g.dev, queries, (const F2FPose*)nullptr, th,
                      nnratio, gw, mw, io);
+}
+
+void launch_search_reloc(const FrameKps& cur, const float* u_right, int64_t ur_stride,
+                         const Camera& cam, const OrbGeomDev& g, const RelocQuery* queries,
+                         const RelocPose* poses, int n_frames, int max_q, const GridWorkspace& gw,
+                         const MatchWorkspace& mw, const MatchIO& io, hipStream_t st) {
+  if (max_q > 0)
+    SLAMGPU_LAUNCH("search_cand", st, search_cand_kernel<RelocQuery>,
+                   dim3((max_q + 4 * (64 / kSearchG) - 1) / (4 * (64 / kSearchG)), n_frames), dim3(256),
+                       0, st, cur, u_right, ur_stride, cam, g.dev, queries, poses, 0, gw, mw, io);
+  SLAMGPU_LAUNCH("search_resolve", st, search_resolve_kernel<RelocQuery>, dim3(n_frames), dim3(64), 0, st, cur,
+                     u_right, ur_stride, cam, g.dev, queries, poses, 0, 0.0f, gw, mw, io);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -90,6 +90,7 @@ int compute_geometry(const OrbParams& p, int cols, int rows, OrbGeom* g,
   g->nlevels = p.nlevels;
   g->cols = cols;
   g->rows = rows;
+  g->log_scale_factor = std::log(p.scale_factor);
   g->nfeatures = p.nfeatures;
   g->ini_th = p.ini_th_fast;
   g->min_th = p.min_th_fast;

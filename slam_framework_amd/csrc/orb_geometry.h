@@ -134,6 +134,8 @@ struct OrbGeom {
   // wt[1][0..1], one[0][0..1], one[1][0..1]} (see orient_desc_kernel)
   uint32_t od_band[3][64][4];
   uint32_t od_ic[64][8];
+  // Frame::log_scale_factor_ = std::log(scale_factor_) (frame.cpp:214): PredictScale(dist, Frame*)
+  float log_scale_factor;
 };
 
 // Resize tables (HResizeLinear / VResizeLinear coefficients, 11-bit fixed point).

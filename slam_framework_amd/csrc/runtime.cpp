@@ -8,6 +8,8 @@
 // OrbMatcher::SearchByProjection (orb_matcher.cpp:13, :1312).
 #include <hip/hip_runtime.h>
 
+#include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -127,6 +129,20 @@ static int dalloc(slamgpu_ctx* c, T** p, size_t count) {
     return slot(c).fail(SLAMGPU_EHIP, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
   c->allocs.push_back(q);
   *p = static_cast<T*>(q);
+  return 0;
+}
+
+// The matchers' per-query workspace (candidate keys, rotation bins): sized at creation for
+// max_frames * kp_cap queries, grown by the calls that may allocate.
+static int ensure_match_ws(slamgpu_ctx* c, int total_queries) {
+  if (total_queries <= c->mw_cap) return 0;
+  int cap = std::max(total_queries, 4096);
+  int rc;
+  if ((rc = dalloc(c, &c->mws.topk, (size_t)cap * kTopK))) return rc;
+  if ((rc = dalloc(c, &c->mws.ncand, (size_t)cap))) return rc;
+  if ((rc = dalloc(c, &c->mws.rot_bin, (size_t)cap))) return rc;
+  if ((rc = dalloc(c, &c->mws.best_idx, (size_t)cap))) return rc;
+  c->mw_cap = cap;
   return 0;
 }
 
@@ -344,6 +360,7 @@ int slamgpu_create(int device, const slamgpu_orb_params* p, int cols, int rows, 
   TRY(dalloc(c, &c->d_nm, (size_t)max_frames));
   TRY(dalloc(c, &c->d_mp, (size_t)g.kp_cap));
   TRY(dalloc(c, &c->d_blk, (size_t)g.kp_cap));
+  TRY(ensure_match_ws(c, max_frames * g.kp_cap));  // slamgpu_search_by_projection_reloc_device
   TRY(hcheck(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_res), res_mirror_bytes(g.kp_cap),
                               hipHostMallocDefault)));
   TRY(dalloc(c, &c->d_res, res_mirror_bytes(g.kp_cap)));
@@ -926,18 +943,6 @@ int slamgpu_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 }
 
 // ---- matchers ------------------------------------------------------------------------------
-static int ensure_match_ws(slamgpu_ctx* c, int total_queries) {
-  if (total_queries <= c->mw_cap) return 0;
-  int cap = std::max(total_queries, 4096);
-  int rc;
-  if ((rc = dalloc(c, &c->mws.topk, (size_t)cap * kTopK))) return rc;
-  if ((rc = dalloc(c, &c->mws.ncand, (size_t)cap))) return rc;
-  if ((rc = dalloc(c, &c->mws.rot_bin, (size_t)cap))) return rc;
-  if ((rc = dalloc(c, &c->mws.best_idx, (size_t)cap))) return rc;
-  c->mw_cap = cap;
-  return 0;
-}
-
 
 int slamgpu_search_by_projection_frame_device(slamgpu_ctx* c, const slamgpu_f2f_query* d_q,
                                               int total_queries, const int* d_q_start,
@@ -981,13 +986,42 @@ int slamgpu_search_by_projection_mps_device(slamgpu_ctx* c, const slamgpu_mps_qu
   return 0;
 }
 
+int slamgpu_search_by_projection_reloc_device(slamgpu_ctx* c, const slamgpu_reloc_query* d_q,
+                                              int total_queries, const int* d_q_start,
+                                              const int* d_q_count, int max_queries,
+                                              const slamgpu_reloc_pose* d_poses,
+                                              int32_t* d_map_point, uint8_t* d_blocked,
+                                              int64_t mp_stride, int* d_nmatches, int n_frames,
+                                              void* stream) {
+  if (!c) return SLAMGPU_EINVAL;
+  if (!c->have_cam || n_frames < 1 || n_frames > c->n_frames_last || mp_stride < c->geom.kp_cap ||
+      total_queries < 0 || max_queries < 0 || (max_queries > 0 && !d_q) || !d_q_start ||
+      !d_q_count || !d_poses || !d_map_point || !d_blocked || !d_nmatches)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_reloc_device: bad arguments");
+  // never allocates: the workspace holds max_frames * kp_cap queries from creation on (a
+  // keyframe has at most kp_cap map point slots); the synchronous calls may have grown it
+  if (total_queries > c->mw_cap)
+    return slot(c).fail(SLAMGPU_ECAP,
+                        "search_by_projection_reloc_device: %d queries, the workspace holds %d",
+                        total_queries, c->mw_cap);
+  MatchIO io{d_q_start, d_q_count, d_map_point, d_blocked, d_nmatches, mp_stride};
+  TimerScope ts(c);
+  launch_search_reloc(left_views(c), c->sout.u_right, c->geom.kp_cap, c->cam, c->gd(),
+                      reinterpret_cast<const RelocQuery*>(d_q),
+                      reinterpret_cast<const RelocPose*>(d_poses), n_frames, max_queries, c->gws,
+                      c->mws, io, pick_stream(c, stream));
+  HIPCHECK(c->err, hipGetLastError());
+  return 0;
+}
+
 }  // extern "C"
 
 // Host-buffer matcher calls on one frame of the last frontend/frame call.
+enum { kSearchF2F, kSearchMps, kSearchReloc };
 template <typename QT>
 static int host_search(slamgpu_ctx* c, int frame, const QT* queries, int nq, int32_t* map_point,
                        uint8_t* blocked, int n, int* nmatches, size_t extra_bytes,
-                       const void* extra, bool f2f, float nnratio, int th) {
+                       const void* extra, int kind, float nnratio, int th) {
   if (!c || frame < 0 || frame >= c->n_frames_last || nq < 0 || !map_point || !blocked)
     return SLAMGPU_EINVAL;
   if (n > c->geom.kp_cap) return slot(c).fail(SLAMGPU_EINVAL, "n > kp capacity");
@@ -1022,10 +1056,14 @@ static int host_search(slamgpu_ctx* c, int frame, const QT* queries, int nq, int
   gw.cell_items += (int64_t)frame * kc;
   MatchIO io{c->d_qmeta, c->d_qmeta + 1, c->d_mp, c->d_blk, c->d_nm, kc};
   TimerScope ts(c);
-  if (f2f)
+  if (kind == kSearchF2F)
     launch_search_frame(cur, c->sout.u_right + frame * kc, kc, c->cam, c->gd(),
                         reinterpret_cast<const F2FQuery*>(qb),
                         reinterpret_cast<const F2FPose*>(eb), 1, nq, gw, c->mws, io, st);
+  else if (kind == kSearchReloc)
+    launch_search_reloc(cur, c->sout.u_right + frame * kc, kc, c->cam, c->gd(),
+                        reinterpret_cast<const RelocQuery*>(qb),
+                        reinterpret_cast<const RelocPose*>(eb), 1, nq, gw, c->mws, io, st);
   else
     launch_search_mps(cur, c->sout.u_right + frame * kc, kc, c->cam, c->gd(),
                       reinterpret_cast<const MpsQuery*>(qb), nnratio, th, 1, nq, gw, c->mws, io,
@@ -1049,14 +1087,39 @@ int slamgpu_search_by_projection_frame(slamgpu_ctx* c, int frame, const slamgpu_
                                        uint8_t* blocked, int n, int* nmatches) {
   if (!pose) return SLAMGPU_EINVAL;
   return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, sizeof(slamgpu_f2f_pose),
-                     pose, true, 0.f, 0);
+                     pose, kSearchF2F, 0.f, 0);
 }
 
 int slamgpu_search_by_projection_mps(slamgpu_ctx* c, int frame, const slamgpu_mps_query* q,
                                      int nq, float nnratio, int th, int32_t* map_point,
                                      uint8_t* blocked, int n, int* nmatches) {
-  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, 0, nullptr, false,
+  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, 0, nullptr, kSearchMps,
                      nnratio, th);
+}
+
+int slamgpu_search_by_projection_reloc(slamgpu_ctx* c, int frame, const slamgpu_reloc_query* q,
+                                       int nq, const slamgpu_reloc_pose* pose, int32_t* map_point,
+                                       uint8_t* blocked, int n, int* nmatches) {
+  if (!c) return SLAMGPU_EINVAL;
+  if (!pose || !map_point || !blocked || !nmatches || nq < 0 || (nq > 0 && !q))
+    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_reloc: null argument");
+  if (!c->have_cam || frame < 0 || frame >= c->n_frames_last)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_reloc: frame %d outside [0, %d)",
+                        frame, c->n_frames_last);
+  if (pose->orb_dist < 0 || pose->orb_dist > 256)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_reloc: orb_dist %d outside [0, 256]",
+                        pose->orb_dist);
+  if (!std::isfinite(pose->th))
+    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_reloc: th is not finite");
+  int nk = 0;
+  if (int rc = slamgpu_download_stereo(c, frame, nullptr, nullptr, INT_MAX, &nk)) return rc;
+  if (n != nk)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_reloc: n = %d, the frame has %d "
+                        "keypoints", n, nk);
+  // blocked = "the slot holds a map point" (CurrentFrame.GetMapPoint(i2) != nullptr, :1526)
+  for (int i = 0; i < n; i++) blocked[i] = map_point[i] >= 0;
+  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, sizeof(slamgpu_reloc_pose),
+                     pose, kSearchReloc, 0.f, 0);
 }
 
 }  // extern "C"

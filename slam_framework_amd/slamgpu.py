@@ -32,6 +32,14 @@ MPS_QUERY_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<
                             ("view_cos", "<f4"), ("level", "<i4"), ("in_view", "<i4"),
                             ("is_bad", "<i4"), ("mp_id", "<i4"), ("blocks", "<i4"),
                             ("pad", "<i4", (3,)), ("desc", "u1", (32,))])
+# slamgpu_reloc_query / slamgpu_reloc_pose (include/slamgpu.h): a map point of the relocalisation
+# candidate keyframe, the current frame's pose with the window factor and ORBdist.
+RELOC_QUERY_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("max_dist", "<f4"), ("min_dist", "<f4"),
+                              ("kf_angle", "<f4"), ("mp_id", "<i4"), ("skip", "<i4"),
+                              ("desc", "u1", (32,))])
+RELOC_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)),
+                             ("th", "<f4"), ("orb_dist", "<i4"), ("check_ori", "<i4")])
+assert RELOC_QUERY_DTYPE.itemsize == 64 and RELOC_POSE_DTYPE.itemsize == 72
 # slamgpu_sim3_match (include/slamgpu_optimizer.h): one OptimizeSim3 correspondence.
 SIM3_MATCH_DTYPE = np.dtype([("x1c", "<f4", (3,)), ("x2c", "<f4", (3,)), ("u1", "<f4"),
                              ("v1", "<f4"), ("u2", "<f4"), ("v2", "<f4"), ("octave1", "<i4"),
@@ -77,7 +85,8 @@ EXPORTS = [
     "slamgpu_frame_record_bytes", "slamgpu_pack_frame_records_device",
     "slamgpu_descriptor_distance", "slamgpu_search_by_projection_frame",
     "slamgpu_search_by_projection_mps", "slamgpu_search_by_projection_frame_device",
-    "slamgpu_search_by_projection_mps_device", "slamgpu_debug_level_keys",
+    "slamgpu_search_by_projection_mps_device", "slamgpu_search_by_projection_reloc",
+    "slamgpu_search_by_projection_reloc_device", "slamgpu_debug_level_keys",
     "slamgpu_make_vo_queries_device", "slamgpu_timing_start", "slamgpu_timing_stop",
     "slamgpu_set_extract_fork",
     "slamgpu_trace_marker",
@@ -197,6 +206,10 @@ def lib():
             vp, vp, ip, vp, vp, ip, vp, vp, vp, C.c_int64, vp, ip, vp]
         L.slamgpu_search_by_projection_mps_device.argtypes = [
             vp, vp, ip, vp, vp, ip, fp, ip, vp, vp, C.c_int64, vp, ip, vp]
+        L.slamgpu_search_by_projection_reloc.argtypes = [vp, ip, vp, ip, vp, vp, vp, ip,
+                                                         C.POINTER(ip)]
+        L.slamgpu_search_by_projection_reloc_device.argtypes = [
+            vp, vp, ip, vp, vp, ip, vp, vp, vp, C.c_int64, vp, ip, vp]
         L.slamgpu_debug_level_keys.argtypes = [vp, ip, ip, ip, vp, ip, C.POINTER(ip)]
         L.slamgpu_make_vo_queries_device.argtypes = [vp, vp, ip, vp, vp, vp, ip, vp]
         L.slamgpu_timing_start.argtypes = [vp, C.c_char_p, ip]
@@ -428,6 +441,16 @@ class Context:
             _ptr(d_poses), _ptr(d_map_point), _ptr(d_blocked), mp_stride, _ptr(d_nmatches),
             n_frames, C.c_void_p(stream or 0)))
 
+    def search_by_projection_reloc_device(self, d_queries, total_queries, d_q_start, d_q_count,
+                                          max_queries, d_poses, d_map_point, d_blocked, mp_stride,
+                                          d_nmatches, n_frames, stream=None):
+        """slamgpu_search_by_projection_reloc_device: RELOC_QUERY / RELOC_POSE records, one pose
+        per frame; d_blocked = "the slot holds a map point". Never allocates or synchronises."""
+        self.check(lib().slamgpu_search_by_projection_reloc_device(
+            self.h, _ptr(d_queries), total_queries, _ptr(d_q_start), _ptr(d_q_count), max_queries,
+            _ptr(d_poses), _ptr(d_map_point), _ptr(d_blocked), mp_stride, _ptr(d_nmatches),
+            n_frames, C.c_void_p(stream or 0)))
+
     def set_extract_fork(self, on):
         """Level 0's FAST beside the pyramid on a side stream (True, the default) or after it
         (False: a timing pass then sees each kernel alone)."""
@@ -460,6 +483,19 @@ class Context:
         nm = C.c_int()
         self.check(lib().slamgpu_search_by_projection_mps(
             self.h, frame, _ptr(queries), len(queries), nnratio, th, _ptr(map_point),
+            _ptr(blocked), len(map_point), C.byref(nm)))
+        return nm.value
+
+    def search_by_projection_reloc(self, frame, queries, pose, map_point, blocked):
+        """slamgpu_search_by_projection_reloc on frame `frame`: map_point (int32 per keypoint,
+        -1 = none) is in/out, blocked (uint8) returns as map_point >= 0. Returns nmatches."""
+        queries = np.ascontiguousarray(queries, dtype=RELOC_QUERY_DTYPE)
+        pose = np.ascontiguousarray(np.atleast_1d(pose), dtype=RELOC_POSE_DTYPE)
+        assert map_point.dtype == np.int32 and blocked.dtype == np.uint8
+        assert len(map_point) == len(blocked)
+        nm = C.c_int()
+        self.check(lib().slamgpu_search_by_projection_reloc(
+            self.h, frame, _ptr(queries), len(queries), _ptr(pose), _ptr(map_point),
             _ptr(blocked), len(map_point), C.byref(nm)))
         return nm.value
 
@@ -591,6 +627,38 @@ class ORBextractor:
         return [self.ctx.pyramid_level(0, l) for l in range(self.nlevels)]
 
 
+def reloc_pose(Tcw, th, orb_dist, check_ori):
+    """RELOC_POSE record of a 4x4 camera pose: Rcw, tcw and Ow = -Rcw.t() * tcw (products and sum
+    in double, one rounding to float: slamgpu_adapter::reloc_camera_center)."""
+    T = np.asarray(Tcw, np.float32).reshape(4, 4)
+    p = np.zeros(1, RELOC_POSE_DTYPE)
+    p["Rcw"] = T[:3, :3].reshape(-1)
+    p["tcw"] = T[:3, 3]
+    for k in range(3):
+        p["Ow"][0, k] = -(float(T[0, k]) * float(T[0, 3]) + float(T[1, k]) * float(T[1, 3]) +
+                          float(T[2, k]) * float(T[2, 3]))
+    p["th"], p["orb_dist"], p["check_ori"] = th, int(orb_dist), int(bool(check_ori))
+    return p
+
+
+def reloc_queries(kf, already_found, Tcw, th, orb_dist, check_ori):
+    """The keyframe's GetMapPointMatches() in keypoint order as RELOC_QUERY records (skip = no
+    point, or in already_found) and the RELOC_POSE record."""
+    mps = np.asarray(kf.map_points, np.int64)
+    q = np.zeros(len(mps), RELOC_QUERY_DTYPE)
+    q["kf_angle"] = np.asarray(kf.keypoints)["angle"]
+    found = set(int(i) for i in already_found)
+    for i, m in enumerate(mps):
+        m = int(m)
+        if m < 0 or m in found:
+            q["skip"][i] = 1
+            continue
+        xyz, max_dist, min_dist, desc = kf.points[m]
+        q["xyz"][i], q["max_dist"][i], q["min_dist"][i], q["desc"][i] = xyz, max_dist, min_dist, desc
+        q["mp_id"][i] = m
+    return q, reloc_pose(Tcw, th, orb_dist, check_ori)
+
+
 class OrbMatcher:
     """Reference-shaped OrbMatcher (orb_matcher.h:14-119) for the per-frame searches."""
     TH_LOW, TH_HIGH, HISTO_LENGTH = 50, 100, 30
@@ -705,6 +773,18 @@ class OrbMatcher:
         ids = np.arange(len(points)) if point_ids is None else np.asarray(point_ids)
         vpMatched[sel] = ids[kp_point[sel]]
         return nm
+
+    def SearchByProjectionReloc(self, ctx, frame, kf, already_found, th, ORBdist, Tcw,
+                                vpMapPoints):
+        """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
+        (orb_matcher.cpp:1455-1582) on frame `frame` of `ctx`'s last frame call.
+        kf: .keypoints (undistorted, for the angles), .map_points (map point id per keypoint, -1 =
+        none or bad), .points (dict id -> (xyz, max_dist, min_dist, desc[32])); already_found: ids
+        of sAlreadyFound; Tcw: the frame's 4x4 pose; vpMapPoints: the frame's map point id per
+        keypoint (int32, -1 = none), updated in place. Returns nmatches."""
+        q, pose = reloc_queries(kf, already_found, Tcw, th, ORBdist, self.mbCheckOrientation)
+        blocked = np.zeros(len(vpMapPoints), np.uint8)
+        return ctx.search_by_projection_reloc(frame, q, pose, vpMapPoints, blocked)
 
     def FuseSim3(self, kf, Scw, points, th, cam, levels, grid):
         """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (orb_matcher.cpp:956-1079): the per-point
