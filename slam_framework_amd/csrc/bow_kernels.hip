@@ -20,32 +20,19 @@
 //   distinctive   MapPoint::ComputeDistinctiveDescriptors (src/data/map_point.cpp:249-304): a wave
 //                 per map point, a lane per row of the distance matrix; nth_element's median is the
 //                 smallest d with #(row <= d) > (n - 1) / 2, found by bisection over [0, 256].
+// The descriptor distance, the rotation bins and the histogram tail are orbmatch_device.h's.
 //   gray          cv::cvtColor(*2GRAY, 8U) as Tracker::GrabImageStereo applies it
 //                 (tracker.cpp:110-127): OpenCV 3.3.1 RGB2Gray<uchar> fixed-point weights.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bow_kernels.h"
-#include "device_math.h"
+#include "orbmatch_device.h"
 #include "timing.h"
 
 namespace slamgpu {
 
 namespace {
-
-constexpr int kThLow = 50, kHisto = 30;  // OrbMatcher TH_LOW, HISTO_LENGTH (orb_matcher.cpp:5-7)
-
-__device__ __forceinline__ int hamming_q(const uint4& a0, const uint4& a1, const uint4& b0,
-                                         const uint4& b1) {
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-__device__ __forceinline__ void load_desc(const uint8_t* p, uint4* d0, uint4* d1) {
-  const uint4* q = reinterpret_cast<const uint4*>(p);
-  *d0 = q[0];
-  *d1 = q[1];
-}
 
 // ---------------------------------------------------------------------------------------
 constexpr int kDescPerBlock = 16;  // 256 threads = 16 rows of 16 lanes
@@ -60,8 +47,7 @@ __global__ __launch_bounds__(256) void bow_descend_kernel(VocabDev v,
   const uint32_t l16 = threadIdx.x & 15;
   const int n = min(counts[(int64_t)set * count_step], o.cap);
   if (f >= n) return;  // the whole row leaves together
-  uint4 x0, x1;
-  load_desc(desc + ((int64_t)set * set_stride + f) * 32, &x0, &x1);
+  const Desc x = load_desc(desc + ((int64_t)set * set_stride + f) * 32);
   uint32_t first = v.root_first, cnt = v.root_count, node = 0, nid = 0;
   int level = 0;
   for (;;) {
@@ -71,7 +57,7 @@ __global__ __launch_bounds__(256) void bow_descend_kernel(VocabDev v,
       const uint32_t c = c0 + l16;
       if (c < cnt) {
         const uint4* s = v.slot_desc + 2 * (size_t)(first + c);
-        best = min(best, (uint32_t)hamming_q(x0, x1, s[0], s[1]) << 16 | c);
+        best = min(best, (uint32_t)hamming(x, Desc{s[0], s[1]}) << 16 | c);
       }
     }
 #pragma unroll
@@ -238,10 +224,7 @@ __global__ __launch_bounds__(64 * kSbWaves) void search_bow_kernel(
     int check_ori, int32_t* __restrict__ match, int64_t match_stride,
     int32_t* __restrict__ nmatches) {
   __shared__ int8_t s_bin[kBowMaxFeatures];
-  __shared__ int s_hist[kHisto];
-  __shared__ int s_acc[kSbWaves];
-  __shared__ int s_rem[kSbWaves];
-  __shared__ int s_ind[3];
+  __shared__ int s_hist[kRotWords<kSbWaves>];
   const int pair = blockIdx.x;
   const BowView A = av[pair], B = bv[pair];
   const int na = *A.n, nb = *B.n, ann = *A.n_nodes, bnn = *B.n_nodes;
@@ -272,8 +255,7 @@ __global__ __launch_bounds__(64 * kSbWaves) void search_bow_kernel(
     for (int p = A.node_start[ia]; p < A.node_start[ia + 1]; p++) {
       const int fa = (int)A.node_feats[p];
       if (A.valid && !A.valid[fa]) continue;
-      uint4 x0, x1;
-      load_desc(A.desc + (int64_t)fa * 32, &x0, &x1);
+      const Desc x = load_desc(A.desc + (int64_t)fa * 32);
       // this lane's best (distance << 16 | position) and second-best distance
       uint32_t m1 = 0xffffffffu, m2 = 256;
       for (int c = 0; c * 64 < nbn; c++) {
@@ -281,9 +263,7 @@ __global__ __launch_bounds__(64 * kSbWaves) void search_bow_kernel(
         if (pos < nbn && !((taken >> c) & 1)) {
           const int fb = (int)B.node_feats[b0 + pos];
           if (!B.valid || B.valid[fb]) {
-            uint4 y0, y1;
-            load_desc(B.desc + (int64_t)fb * 32, &y0, &y1);
-            const uint32_t d = (uint32_t)hamming_q(x0, x1, y0, y1);
+            const uint32_t d = (uint32_t)hamming(x, B.desc + (int64_t)fb * 32);
             const uint32_t k = d << 16 | (uint32_t)pos;
             if (k < m1) {
               if (m1 != 0xffffffffu) m2 = min(m2, m1 >> 16);
@@ -308,10 +288,7 @@ __global__ __launch_bounds__(64 * kSbWaves) void search_bow_kernel(
           const int fb = (int)B.node_feats[b0 + pos];
           out[fa] = fb;
           if (check_ori) {
-            float rot = A.kps[fa].angle - B.kps[fb].angle;
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / kHisto));
-            if (bin == kHisto) bin = 0;
+            const int bin = rot_bin(A.kps[fa].angle, B.kps[fb].angle);
             s_bin[fa] = (int8_t)bin;
             atomicAdd(&s_hist[bin], 1);
           }
@@ -320,53 +297,8 @@ __global__ __launch_bounds__(64 * kSbWaves) void search_bow_kernel(
       }
     }
   }
-  if (lane == 0) s_acc[wid] = acc;
-  __syncthreads();
-  if (tid == 0) {  // ComputeThreeMaxima (orb_matcher.cpp:1584-1625)
-    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int i = 0; i < kHisto; i++) {
-      const int s = s_hist[i];
-      if (s > max1) {
-        max3 = max2; max2 = max1; max1 = s;
-        i3 = i2; i2 = i1; i1 = i;
-      } else if (s > max2) {
-        max3 = max2; max2 = s;
-        i3 = i2; i2 = i;
-      } else if (s > max3) {
-        max3 = s;
-        i3 = i;
-      }
-    }
-    if (max2 < 0.1f * (float)max1) {
-      i2 = -1;
-      i3 = -1;
-    } else if (max3 < 0.1f * (float)max1) {
-      i3 = -1;
-    }
-    s_ind[0] = i1;
-    s_ind[1] = i2;
-    s_ind[2] = i3;
-  }
-  __syncthreads();
-  int removed = 0;
-  if (check_ori) {
-    const int i1 = s_ind[0], i2 = s_ind[1], i3 = s_ind[2];
-    for (int i = tid; i < na; i += 64 * kSbWaves) {
-      const int bin = s_bin[i];
-      if (bin >= 0 && bin != i1 && bin != i2 && bin != i3) {
-        out[i] = -1;
-        removed++;
-      }
-    }
-  }
-  removed = wave_sum(removed);
-  if (lane == 0) s_rem[wid] = removed;
-  __syncthreads();
-  if (tid == 0) {
-    int nm = 0;
-    for (int w = 0; w < kSbWaves; w++) nm += s_acc[w] - s_rem[w];
-    nmatches[pair] = nm;
-  }
+  const int nm = rot_filter_count<kSbWaves>(acc, check_ori, s_hist, s_bin, na, out);
+  if (tid == 0) nmatches[pair] = nm;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -388,16 +320,13 @@ __global__ __launch_bounds__(256) void distinctive_kernel(const uint8_t* __restr
   for (int i0 = 0; i0 < n; i0 += 64) {
     const int i = i0 + lane;
     if (i < n) {
-      uint4 x0, x1;
-      load_desc(D + (int64_t)i * 32, &x0, &x1);
+      const Desc x = load_desc(D + (int64_t)i * 32);
       int lo = 0, hi = 256;  // the half-th smallest of row i (0 on the diagonal)
       while (lo < hi) {
         const int mid = (lo + hi) >> 1;
         int cnt = 0;
         for (int j = 0; j < n; j++) {
-          uint4 y0, y1;
-          load_desc(D + (int64_t)j * 32, &y0, &y1);
-          cnt += (j == i ? 0 : hamming_q(x0, x1, y0, y1)) <= mid;
+          cnt += (j == i ? 0 : hamming(x, D + (int64_t)j * 32)) <= mid;
         }
         if (cnt > half) hi = mid;
         else lo = mid + 1;

@@ -247,6 +247,46 @@ __device__ __forceinline__ double lane_partner(double v, int M) {
   return __builtin_bit_cast(double, hi << 32 | lo);
 }
 
+// Reductions over groups of G lanes (G = 16: a DPP row; 64: the wave) by that butterfly: every
+// lane ends with its group's result. Keys are compared as unsigned integers.
+template <int G>
+__device__ __forceinline__ uint32_t group_min_key(uint32_t v) {
+#pragma unroll
+  for (int M = G / 2; M >= 1; M >>= 1) v = min(v, lane_partner_u32(v, M));
+  return v;
+}
+template <int G>
+__device__ __forceinline__ uint64_t group_min_key(uint64_t v) {
+#pragma unroll
+  for (int M = G / 2; M >= 1; M >>= 1) {
+    const uint64_t o = (uint64_t)lane_partner_u32((uint32_t)(v >> 32), M) << 32 |
+                       lane_partner_u32((uint32_t)v, M);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+template <int G>
+__device__ __forceinline__ int group_sum(int v) {
+#pragma unroll
+  for (int M = G / 2; M >= 1; M >>= 1) v += (int)lane_partner_u32((uint32_t)v, M);
+  return v;
+}
+// Inclusive prefix sum over each group of G lanes: DPP row shifts within each row of 16 lanes,
+// then (G = 64) the row totals carried by row_bcast:15 / row_bcast:31.
+template <int G>
+__device__ __forceinline__ int group_incl_scan(int v) {
+  static_assert(G == 16 || G == 64, "groups are DPP rows or the wave");
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);  // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);  // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);  // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);  // row_shr:8
+  if constexpr (G == 64) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
+    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
+  }
+  return v;
+}
+
 // Number of set bits of `mask` strictly below this lane.
 __device__ __forceinline__ int lanes_below(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),

@@ -12,7 +12,8 @@
 //                across lanes, in GetFeaturesInArea order (grid cell x-major, then index): the
 //                first strict minimum is the minimum of (distance, cell, index).
 // Float semantics follow oracle/kfmatch_oracle.c (the Release build's contractions as explicit
-// fmaf, OpenCV's double sums).
+// fmaf, OpenCV's double sums). The rules shared with the other matchers (descriptor distance,
+// Fuse's gate chain, grid cells, candidate keys, the rotation histogram) are orbmatch_device.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -41,8 +42,7 @@ __global__ __launch_bounds__(64 * kTriWaves) void search_tri_kernel(
     slamgpu_camera cam, slamgpu_levels lv, int check_ori, int32_t* __restrict__ match,
     int64_t match_stride, int32_t* __restrict__ nmatches) {
   __shared__ int8_t s_bin[kMaxFeat];
-  __shared__ int s_hist[kHisto];
-  __shared__ int s_acc[kTriWaves], s_rem[kTriWaves], s_ind[3], s_bad;
+  __shared__ int s_hist[kRotWords<kTriWaves>], s_bad;
   const int pair = blockIdx.x, tid = threadIdx.x, lane = lane_id(), wid = wave_id();
   const slamgpu_tri_pair P = pairs[pair];
   const slamgpu_kf& A = kfs[P.kf1];
@@ -127,63 +127,15 @@ __global__ __launch_bounds__(64 * kTriWaves) void search_tri_kernel(
       const int idx2 = (int)B.node_feats[b0 + (0xffff - (int)(best & 0xffffu))];
       out[idx1] = idx2;
       if (check_ori) {
-        float rot = kp1.angle - B.kps[idx2].angle;
-        if (rot < 0.0f) rot += 360.0f;
-        int bin = (int)roundf(rot * (1.0f / kHisto));
-        if (bin == kHisto) bin = 0;
+        const int bin = rot_bin(kp1.angle, B.kps[idx2].angle);
         s_bin[idx1] = (int8_t)bin;
         atomicAdd(&s_hist[bin], 1);
       }
     }
     acc++;
   }
-  if (lane == 0) s_acc[wid] = acc;
-  __syncthreads();
-  if (tid == 0) {  // ComputeThreeMaxima (orb_matcher.cpp:1584-1625)
-    int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-    for (int i = 0; i < kHisto; i++) {
-      const int s = s_hist[i];
-      if (s > m1) {
-        m3 = m2; m2 = m1; m1 = s;
-        i3 = i2; i2 = i1; i1 = i;
-      } else if (s > m2) {
-        m3 = m2; m2 = s;
-        i3 = i2; i2 = i;
-      } else if (s > m3) {
-        m3 = s;
-        i3 = i;
-      }
-    }
-    if (m2 < 0.1f * (float)m1) {
-      i2 = -1;
-      i3 = -1;
-    } else if (m3 < 0.1f * (float)m1) {
-      i3 = -1;
-    }
-    s_ind[0] = i1;
-    s_ind[1] = i2;
-    s_ind[2] = i3;
-  }
-  __syncthreads();
-  int removed = 0;
-  if (check_ori) {
-    const int i1 = s_ind[0], i2 = s_ind[1], i3 = s_ind[2];
-    for (int i = tid; i < na; i += 64 * kTriWaves) {
-      const int bin = s_bin[i];
-      if (bin >= 0 && bin != i1 && bin != i2 && bin != i3) {
-        out[i] = -1;
-        removed++;
-      }
-    }
-  }
-  removed = wave_sum(removed);
-  if (lane == 0) s_rem[wid] = removed;
-  __syncthreads();
-  if (tid == 0) {
-    int nm = 0;
-    for (int w = 0; w < kTriWaves; w++) nm += s_acc[w] - s_rem[w];
-    nmatches[pair] = s_bad ? -1 : nm;
-  }
+  const int nm = rot_filter_count<kTriWaves>(acc, check_ori, s_hist, s_bin, na, out);
+  if (tid == 0) nmatches[pair] = s_bad ? -1 : nm;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -204,39 +156,21 @@ __global__ __launch_bounds__(256) void fuse_kernel(const slamgpu_kf* __restrict_
   const int n = min(K.n, kMaxFeat);
   do {
     if (P.skip) break;
-    const float xc = gemm_row(K.Rcw, P.xyz, K.tcw[0]);
-    const float yc = gemm_row(K.Rcw + 3, P.xyz, K.tcw[1]);
-    const float zc = gemm_row(K.Rcw + 6, P.xyz, K.tcw[2]);
-    if (zc < 0.0f) break;
-    const float invz = 1.0f / zc;
-    const float x = xc * invz, y = yc * invz;
-    const float u = fmaf(cam.fx, x, cam.cx), v = fmaf(cam.fy, y, cam.cy);
-    if (!(u >= g.min_x && u < g.max_x && v >= g.min_y && v < g.max_y)) break;
-    const float urp = fmaf(-cam.bf, invz, u);
-    const float maxD = 1.2f * P.max_dist, minD = 0.8f * P.min_dist;
-    const float po0 = P.xyz[0] - K.Ow[0], po1 = P.xyz[1] - K.Ow[1], po2 = P.xyz[2] - K.Ow[2];
-    double s = 0.0;
-    s += (double)po0 * (double)po0;
-    s += (double)po1 * (double)po1;
-    s += (double)po2 * (double)po2;
-    const float dist3D = (float)sqrt(s);
-    if (dist3D < minD || dist3D > maxD) break;
-    double dot = 0.0;
-    dot += (double)po0 * (double)P.normal[0];
-    dot += (double)po1 * (double)P.normal[1];
-    dot += (double)po2 * (double)P.normal[2];
-    if (dot < 0.5 * (double)dist3D) break;
-    int lvl = (int)ceilf(glibc_logf(P.max_dist / dist3D) / lv.log_scale_factor);
-    lvl = lvl < 0 ? 0 : (lvl >= lv.nlevels ? lv.nlevels - 1 : lvl);
-    const float r = th * lv.scale[lvl];
-    int cx0, cx1, cy0, cy1;
-    if (!grid_window(u, v, r, g, &cx0, &cx1, &cy0, &cy1)) break;
-    uint64_t best = ~0ull;
+    Proj pr;
+    if (!project_scw(K, P, th, cam, lv, g, &pr)) break;
+    const float u = pr.u, v = pr.v, r = pr.r;
+    const int lvl = pr.lvl;
+    const float urp = fmaf(-cam.bf, pr.invz, u);
+    uint64_t best = kNoKey;
     for (int j = lane; j < n; j += 64) {
       const slamgpu_keypoint kp = K.kps[j];
-      int px, py;
-      kp_cell(kp.x, kp.y, g, &px, &py);
-      if (px < cx0 || px > cx1 || py < cy0 || py > cy1) continue;  // also drops off-grid kps
+      // the window test also drops off-grid and non-finite kps; only a cell inside the window
+      // becomes an int, and the row is worked out only for a keypoint in the window's columns
+      const float fx = cell_coord(kp.x, g.min_x, g.cell_w);
+      if (!(fx >= (float)pr.cx0 && fx <= (float)pr.cx1)) continue;
+      const float fy = cell_coord(kp.y, g.min_y, g.cell_h);
+      if (!(fy >= (float)pr.cy0 && fy <= (float)pr.cy1)) continue;
+      const int px = (int)fx, py = (int)fy;
       const float dxk = kp.x - u, dyk = kp.y - v;
       if (!(fabsf(dxk) < r && fabsf(dyk) < r)) continue;
       const int kl = kp.octave;
@@ -252,13 +186,13 @@ __global__ __launch_bounds__(256) void fuse_kernel(const slamgpu_kf* __restrict_
         if ((double)(e2 * lv.inv_sigma2[kl]) > 5.99) continue;
       }
       const uint32_t dist = (uint32_t)hamming32(P.desc, K.desc + (int64_t)j * 32);
-      const uint64_t key = (uint64_t)dist << 32 | (uint64_t)(px * kGridRows + py) << 12 | (uint32_t)j;
+      const uint64_t key = cand_key(dist, px * kGridRows + py, j);
       best = best < key ? best : key;
     }
     best = wave_min(best);
-    if (best == ~0ull) break;
-    out_dist = (int)(best >> 32);
-    if (out_dist <= kThLow) out_idx = (int)(best & 0xfffu);
+    if (best == kNoKey) break;
+    out_dist = key_dist(best);
+    if (out_dist <= kThLow) out_idx = key_idx(best);
   } while (false);
   if (lane == 0) {
     best_idx[i] = out_idx;

@@ -1,56 +1,22 @@
-// kfmatch_common.h -- what kfmatch.hip (LocalMapper matchers) and loopmatch.hip (LoopCloser
-// matchers) share: the descriptor distance, OpenCV's small gemm row, the KeyFrame grid-window
-// arithmetic of GetFeaturesInArea, and the host side of a keyframe: its validation and its place in
-// and upload to the staging buffer (host_stage.h; errors go to t_kf_err).
+// kfmatch_common.h -- the host side of a keyframe that kfmatch.hip (LocalMapper matchers) and
+// loopmatch.hip (LoopCloser matchers) share: its validation and its place in and upload to the
+// staging buffer (host_stage.h; errors go to t_kf_err). The matchers' device rules are in
+// orbmatch_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/slamgpu_kfmatch.h"
-#include "device_math.h"
 #include "host_stage.h"
+#include "orbmatch_device.h"
 #include "stage_layout.h"
 
 namespace slamgpu {
 
-constexpr int kThLow = 50, kThHigh = 100, kHisto = 30, kGridCols = 64, kGridRows = 48;
 constexpr int kMaxFeat = SLAMGPU_KF_MAX_FEATURES;
 
 static_assert(sizeof(slamgpu_kf) == 128, "slamgpu_kf layout");
 static_assert(sizeof(slamgpu_fuse_point) == 80, "slamgpu_fuse_point layout");
-
-__device__ __forceinline__ int hamming32(const uint8_t* a, const uint8_t* b) {
-  const uint4* p = reinterpret_cast<const uint4*>(a);
-  const uint4* q = reinterpret_cast<const uint4*>(b);
-  const uint4 a0 = p[0], a1 = p[1], b0 = q[0], b1 = q[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
-
-// OpenCV's small float gemm row (Rcw * X + tcw): float dot, then (double) add.
-__device__ __forceinline__ float gemm_row(const float* R, const float* x, float c) {
-  const float dot = R[0] * x[0] + R[1] * x[1] + R[2] * x[2];
-  return (float)((double)dot + (double)c);
-}
-
-// KeyFrame::GetFeaturesInArea (keyframe.cpp:442-476) cell window of a search square of half
-// side r around (u, v); false when the window misses the grid.
-__device__ __forceinline__ bool grid_window(float u, float v, float r, const slamgpu_kf_grid& g,
-                                            int* cx0, int* cx1, int* cy0, int* cy1) {
-  *cx0 = max(0, (int)floorf((u - g.min_x - r) / g.cell_w));
-  *cx1 = min(kGridCols - 1, (int)ceilf((u - g.min_x + r) / g.cell_w));
-  *cy0 = max(0, (int)floorf((v - g.min_y - r) / g.cell_h));
-  *cy1 = min(kGridRows - 1, (int)ceilf((v - g.min_y + r) / g.cell_h));
-  return !(*cx1 < 0 || *cx0 >= kGridCols || *cy1 < 0 || *cy0 >= kGridRows);
-}
-
-// Frame::PosInGrid (frame.cpp:339-346): the cell AssignFeaturesToGrid put a keypoint in (a cell
-// outside the 64 x 48 grid means the keypoint is in no cell).
-__device__ __forceinline__ void kp_cell(float x, float y, const slamgpu_kf_grid& g, int* px,
-                                        int* py) {
-  *px = (int)roundf((x - g.min_x) / g.cell_w);
-  *py = (int)roundf((y - g.min_y) / g.cell_h);
-}
 
 inline int check_levels(const slamgpu_levels* lv) {
   if (!lv || lv->nlevels < 1 || lv->nlevels > 32)

@@ -19,7 +19,9 @@
 // (distance, cell, index), cells in GetFeaturesInArea's x-major order: the reference's first
 // strict minimum. None of the three applies Fuse's chi-square gates or reads u_right.
 // Float semantics follow oracle/kfmatch_oracle.c (explicit fmaf for u, v; OpenCV's gemm row as a
-// float dot plus a double add; cv::norm and Mat::dot as double sums; glibc logf).
+// float dot plus a double add; cv::norm and Mat::dot as double sums; glibc logf); the gates
+// (project_scw and its parts), the descriptor distance and the candidate keys are
+// orbmatch_device.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -49,75 +51,13 @@ __device__ __forceinline__ void stage_kps(KpLds& S, const slamgpu_kf& K, int n,
   for (int j = tid; j < n; j += nthreads) {
     const slamgpu_keypoint kp = K.kps[j];
     int px, py;
-    kp_cell(kp.x, kp.y, g, &px, &py);
-    const bool on = px >= 0 && px < kGridCols && py >= 0 && py < kGridRows;
+    const bool on = pos_in_grid(kp.x, kp.y, g.min_x, g.min_y, g.cell_w, g.cell_h, &px, &py);
     const int o = kp.octave;
     S.x[j] = kp.x;
     S.y[j] = kp.y;
     S.c[j] = make_uchar4(on ? px : 255, on ? py : 255, (o >= 0 && o < 255) ? o : 255,
                          (excl && excl[j]) ? 1 : 0);
   }
-}
-
-struct Proj {
-  float u, v, r;
-  int lvl, cx0, cx1, cy0, cy1;
-};
-
-// The camera-frame point to the image: positive depth, projection, IsInImage.
-__device__ __forceinline__ bool proj_uv(float xc, float yc, float zc, const slamgpu_camera& cam,
-                                        const slamgpu_kf_grid& g, Proj* o) {
-  if (zc < 0.0f) return false;
-  const float invz = 1.0f / zc;
-  const float x = xc * invz, y = yc * invz;
-  o->u = fmaf(cam.fx, x, cam.cx);
-  o->v = fmaf(cam.fy, y, cam.cy);
-  return o->u >= g.min_x && o->u < g.max_x && o->v >= g.min_y && o->v < g.max_y;
-}
-
-// Get{Min,Max}DistanceInvariance (map_point.cpp:356-364) around the distance the method measures.
-__device__ __forceinline__ bool in_range(const slamgpu_fuse_point& P, float dist3D) {
-  const float maxD = 1.2f * P.max_dist, minD = 0.8f * P.min_dist;
-  return !(dist3D < minD || dist3D > maxD);
-}
-
-// PredictScale, the search radius and its cell window.
-__device__ __forceinline__ bool proj_window(const slamgpu_fuse_point& P, float dist3D, float th,
-                                            const slamgpu_levels& lv, const slamgpu_kf_grid& g,
-                                            Proj* o) {
-  int lvl = (int)ceilf(glibc_logf(P.max_dist / dist3D) / lv.log_scale_factor);
-  lvl = lvl < 0 ? 0 : (lvl >= lv.nlevels ? lv.nlevels - 1 : lvl);
-  o->lvl = lvl;
-  o->r = th * lv.scale[lvl];
-  return grid_window(o->u, o->v, o->r, g, &o->cx0, &o->cx1, &o->cy0, &o->cy1);
-}
-
-__device__ __forceinline__ float norm3(float a, float b, float c) {
-  double s = 0.0;
-  s += (double)a * (double)a;
-  s += (double)b * (double)b;
-  s += (double)c * (double)c;
-  return (float)sqrt(s);
-}
-
-// The gates of Fuse(pKF, Scw, ...) :988-1028 and SearchByProjection(pKF, Scw, ...) :415-454.
-__device__ __forceinline__ bool project_scw(const slamgpu_kf& K, const slamgpu_fuse_point& P,
-                                            float th, const slamgpu_camera& cam,
-                                            const slamgpu_levels& lv, const slamgpu_kf_grid& g,
-                                            Proj* o) {
-  const float xc = gemm_row(K.Rcw, P.xyz, K.tcw[0]);
-  const float yc = gemm_row(K.Rcw + 3, P.xyz, K.tcw[1]);
-  const float zc = gemm_row(K.Rcw + 6, P.xyz, K.tcw[2]);
-  if (!proj_uv(xc, yc, zc, cam, g, o)) return false;
-  const float po0 = P.xyz[0] - K.Ow[0], po1 = P.xyz[1] - K.Ow[1], po2 = P.xyz[2] - K.Ow[2];
-  const float dist3D = norm3(po0, po1, po2);
-  if (!in_range(P, dist3D)) return false;
-  double dot = 0.0;
-  dot += (double)po0 * (double)P.normal[0];
-  dot += (double)po1 * (double)P.normal[1];
-  dot += (double)po2 * (double)P.normal[2];
-  if (dot < 0.5 * (double)dist3D) return false;
-  return proj_window(P, dist3D, th, lv, g, o);
 }
 
 // The gates of SearchBySim3 :1142-1173 (and :1222-1253): source keyframe A's point into the
@@ -139,26 +79,7 @@ __device__ __forceinline__ bool project_sim3(const slamgpu_kf& A, const float* s
   return proj_window(P, dist3D, th, lv, g, o);
 }
 
-struct Desc {
-  uint4 a, b;
-};
-
-__device__ __forceinline__ Desc load_desc(const uint8_t* d) {
-  const uint4* p = reinterpret_cast<const uint4*>(d);
-  return Desc{p[0], p[1]};
-}
-
-__device__ __forceinline__ int hamming(const Desc& p, const uint8_t* d) {
-  const uint4* q = reinterpret_cast<const uint4*>(d);
-  const uint4 b0 = q[0], b1 = q[1];
-  return __popc(p.a.x ^ b0.x) + __popc(p.a.y ^ b0.y) + __popc(p.a.z ^ b0.z) +
-         __popc(p.a.w ^ b0.w) + __popc(p.b.x ^ b1.x) + __popc(p.b.y ^ b1.y) +
-         __popc(p.b.z ^ b1.z) + __popc(p.b.w ^ b1.w);
-}
-
-constexpr uint64_t kNoKey = ~0ull;
-
-// Wave scan of the staged keyframe: the minimum (distance << 32 | cell << 12 | index) over the
+// Wave scan of the staged keyframe: the minimum candidate key (distance, cell, index) over the
 // keypoints inside the window, of octave lvl - 1 or lvl, not excluded, not in `claimed` (LDS
 // bitmap or NULL) and with key > floor (kNoKey: no floor). *n_low (if non-NULL) receives the
 // number of such keypoints, floor aside, of distance <= TH_LOW.
@@ -177,8 +98,7 @@ __device__ __forceinline__ uint64_t scan_kps(const KpLds& S, int n, const Proj& 
     if (claimed && (claimed[j >> 5] >> (j & 31) & 1u)) continue;
     const uint32_t dist = (uint32_t)hamming(d, kdesc + (int64_t)j * 32);
     low += dist <= (uint32_t)kThLow;
-    const uint64_t key =
-        (uint64_t)dist << 32 | (uint64_t)(px * kGridRows + py) << 12 | (uint32_t)j;
+    const uint64_t key = cand_key(dist, px * kGridRows + py, j);
     if (floor != kNoKey && key <= floor) continue;
     best = best < key ? best : key;
   }
@@ -207,8 +127,8 @@ __global__ __launch_bounds__(64 * kScanWaves) void fuse_sim3_kernel(
     if (n > 0 && !skipped && project_scw(K, P, th, cam, lv, g, &pr)) {
       const uint64_t best = scan_kps(S, n, pr, load_desc(P.desc), K.desc, nullptr, kNoKey, nullptr);
       if (best != kNoKey) {
-        out_dist = (int)(best >> 32);
-        if (out_dist <= kThLow) out_idx = (int)(best & 0xfffu);
+        out_dist = key_dist(best);
+        if (out_dist <= kThLow) out_idx = key_idx(best);
       }
     }
     if (lane == 0) {
@@ -252,7 +172,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void sbp_scan_kernel(
       const int nk = min(total, kKeep);
       for (int k = 0; k < nk; k++) {  // the total candidates <= TH_LOW are the first in key order
         if (k > 0) key = scan_kps(S, n, pr, d, K.desc, nullptr, key, nullptr);
-        if (lane == k) mine = (int)(key & 0xfffu);
+        if (lane == k) mine = key_idx(key);
       }
     }
     if (lane == 0) row[0] = total;
@@ -352,7 +272,7 @@ __global__ __launch_bounds__(64) void sbp_resolve_kernel(
       if (!P.skip && project_scw(K, P, th, cam, lv, g, &pr)) {
         const uint64_t key =
             scan_kps(S, n, pr, load_desc(P.desc), K.desc, s_claimed, kNoKey, nullptr);
-        if (key != kNoKey && (int)(key >> 32) <= kThLow) got = (int)(key & 0xfffu);
+        if (key != kNoKey && key_dist(key) <= kThLow) got = key_idx(key);
       }
       if (lane == 0) {
         pkp[start] = got;
@@ -410,7 +330,7 @@ __global__ __launch_bounds__(64 * kScanWaves) void sim3_scan_kernel(
     if (nb > 0 && !X.skip && !already[i] && project_sim3(A, sR, t, X, th, cam, lv, g, &pr)) {
       const uint64_t best =
           scan_kps(S, nb, pr, load_desc(X.desc), B.desc, nullptr, kNoKey, nullptr);
-      if (best != kNoKey && (int)(best >> 32) <= kThHigh) res = (int)(best & 0xfffu);
+      if (best != kNoKey && key_dist(best) <= kThHigh) res = key_idx(best);
     }
     if (lane == 0) out[i] = res;
   }

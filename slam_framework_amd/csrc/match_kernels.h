@@ -4,10 +4,10 @@
 #include <stdint.h>
 
 #include "orb_kernels.h"
+#include "orbmatch_device.h"  // kGridCols, kGridRows
 
 namespace slamgpu {
 
-constexpr int kGridCols = 64, kGridRows = 48;  // Frame::grid_cols / grid_rows (frame.h:104-105)
 constexpr int kGridCells = kGridCols * kGridRows;
 // candidates kept per query for claim resolution: 6 (r5) -- a query whose kept candidates are all
 // claimed by earlier queries is rescanned alone on the resolve chain (4: 0.153 ms/step of

@@ -9,7 +9,8 @@
 //                                                     :1312-1453) + rotation histogram; and the
 //                                                     relocalisation overload (Frame, KeyFrame,
 //                                                     sAlreadyFound, th, ORBdist) :1455-1582
-// Every Hamming distance is popcount(a ^ b) over 4 x u64 (== DescriptorDistance, :1630-1646).
+// Every Hamming distance is popcount(a ^ b) over the 256 bits (== DescriptorDistance,
+// :1630-1646; orbmatch_device.h, which also holds the other rules shared with the keyframe matchers).
 // The projection matchers are greedy in query order (a keypoint taken by an earlier query whose
 // map point has observations is skipped, :59-63 / :1389-1393), so candidate search is parallel
 // over queries and only a short claim-resolution pass per frame is sequential.
@@ -18,22 +19,12 @@
 
 #include <type_traits>
 
-#include "device_math.h"
-#include "timing.h"
 #include "match_kernels.h"
+#include "orbmatch_device.h"
+#include "timing.h"
 #include "undistort.h"
 
 namespace slamgpu {
-
-constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO_LENGTH = 30;
-constexpr uint64_t kNoKey = ~0ull;
-
-__device__ __forceinline__ int hamming32(const uint8_t* a, const uint8_t* b) {
-  const uint64_t* pa = reinterpret_cast<const uint64_t*>(a);
-  const uint64_t* pb = reinterpret_cast<const uint64_t*>(b);
-  return __popcll(pa[0] ^ pb[0]) + __popcll(pa[1] ^ pb[1]) + __popcll(pa[2] ^ pb[2]) +
-         __popcll(pa[3] ^ pb[3]);
-}
 
 // NT-thread exclusive scan of arr[0..n) in place; returns the total. wsum: NT / 64 ints.
 template <int CAP, int NT = 256>
@@ -230,7 +221,7 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(ImageBatch b,
   ok = ok && !(maxU < 0);
   const uint8_t* dL = ext.desc + (il * ext.stride + (ok ? iL : 0)) * 32;
   const uint8_t* dRb = ext.desc + ir * ext.stride * 32;
-  uint32_t best = ((uint32_t)TH_HIGH << 16) | 0xffffu;
+  uint32_t best = ((uint32_t)kThHigh << 16) | 0xffffu;
   float bestU = 0.0f;  // x of this lane's best candidate
   if (ok) {
     // kCandU candidates per lane at a time, each stage's loads all in flight before the next
@@ -271,7 +262,7 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(ImageBatch b,
                            __popc(l0.w ^ r0[u].w) + __popc(l1.x ^ r1[u].x) + __popc(l1.y ^ r1[u].y) +
                            __popc(l1.z ^ r1[u].z) + __popc(l1.w ^ r1[u].w);
           const uint32_t key = ((uint32_t)dist << 16) | (uint32_t)iR[u];
-          if (dist < TH_HIGH && key < best) {
+          if (dist < kThHigh && key < best) {
             best = key;
             bestU = uR[u];
           }
@@ -285,7 +276,7 @@ __global__ __launch_bounds__(256) void stereo_match_kernel(ImageBatch b,
   const uint64_t hit = __ballot(mine == best) & gmask;
   const float uRbest = __shfl(bestU, hit ? __builtin_ctzll(hit) : lane, 64);
   const int bestDist = (int)(best >> 16);
-  const int thOrbDist = (TH_HIGH + TH_LOW) / 2;
+  const int thOrbDist = (kThHigh + kThLow) / 2;
   ok = ok && bestDist < thOrbDist;
   // sliding-window SAD at the left keypoint's level (:481-531)
   const float uR0 = ok ? uRbest : 0.f;
@@ -657,9 +648,8 @@ void launch_stereo(const ImageBatch& b, const OrbGeomDev& gd, const Camera& cam,
 // ---------------------------------------------------------------------------------------
 // Grid (AssignFeaturesToGrid + PosInGrid, frame.cpp:234-248, 339-346).
 __device__ __forceinline__ int grid_cell(const Camera& cam, float x, float y) {
-  const int px = (int)roundf((x - cam.min_x) / cam.cell_w);
-  const int py = (int)roundf((y - cam.min_y) / cam.cell_h);
-  if (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) return -1;
+  int px, py;
+  if (!pos_in_grid(x, y, cam.min_x, cam.min_y, cam.cell_w, cam.cell_h, &px, &py)) return -1;
   return px * kGridRows + py;
 }
 
@@ -779,9 +769,7 @@ void launch_undistort(const FrameKps& src, KeyPoint* dst, int64_t dst_stride, co
 // ---------------------------------------------------------------------------------------
 // Candidate scan of one query by one wave: Frame::GetFeaturesInArea (frame.cpp:348-403) plus the
 // matcher's per-candidate filters, keeping the kTopK best candidates by (distance, position in
-// GetFeaturesInArea order). That order visits cells x-major then y, each cell by keypoint index,
-// so the position key is (ix * 48 + iy, index) -- which makes the lexicographic minimum equal
-// to the first strict-'<' winner of the reference's sequential loop.
+// GetFeaturesInArea order): the candidate keys of orbmatch_device.h.
 struct ScanCtx {
   float x, y, r;         // GetFeaturesInArea(x, y, r, min_level, max_level)
   int min_level, max_level;
@@ -799,104 +787,26 @@ struct FrameView {
   const uint8_t* blocked;
 };
 
-// Wave reductions over the lanes by the permlane / DPP butterfly of lane_partner_u32 (no LDS
-// round trips; every lane ends with the result). Keys are compared as unsigned integers.
-__device__ __forceinline__ uint32_t wave_min_key(uint32_t v) {
-#pragma unroll
-  for (int M = 32; M >= 1; M >>= 1) v = min(v, lane_partner_u32(v, M));
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_min_key(uint64_t v) {
-#pragma unroll
-  for (int M = 32; M >= 1; M >>= 1) {
-    const uint64_t o = (uint64_t)lane_partner_u32((uint32_t)(v >> 32), M) << 32 |
-                       lane_partner_u32((uint32_t)v, M);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int wave_sum_bfly(int v) {
-#pragma unroll
-  for (int M = 32; M >= 1; M >>= 1) v += (int)lane_partner_u32((uint32_t)v, M);
-  return v;
-}
-// Inclusive prefix sum over the 64 lanes: DPP row shifts within each row of 16 lanes, then the
-// row totals carried by row_bcast:15 / row_bcast:31.
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);  // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);  // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);  // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);  // row_shr:8
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
-
-// The same over groups of G lanes (G = 16: a DPP row; 64: the wave); a butterfly level M < 16
-// stays inside a row (lane_partner_u32)
-template <int G>
-__device__ __forceinline__ int group_incl_scan(int v) {
-  static_assert(G == 16 || G == 64, "groups are DPP rows or the wave");
-  if constexpr (G == 64) {
-    return wave_incl_scan(v);
-  } else {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);  // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);  // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);  // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);  // row_shr:8
-    return v;
-  }
-}
-template <int G>
-__device__ __forceinline__ uint32_t group_min_key(uint32_t v) {
-#pragma unroll
-  for (int M = G / 2; M >= 1; M >>= 1) v = min(v, lane_partner_u32(v, M));
-  return v;
-}
-template <int G>
-__device__ __forceinline__ uint64_t group_min_key(uint64_t v) {
-#pragma unroll
-  for (int M = G / 2; M >= 1; M >>= 1) {
-    const uint64_t o = (uint64_t)lane_partner_u32((uint32_t)(v >> 32), M) << 32 |
-                       lane_partner_u32((uint32_t)v, M);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-template <int G>
-__device__ __forceinline__ int group_sum(int v) {
-#pragma unroll
-  for (int M = G / 2; M >= 1; M >>= 1) v += (int)lane_partner_u32((uint32_t)v, M);
-  return v;
-}
-
 // The scan's candidate key, ordered as (distance, cell, index): 32 bits -- dist (<= 256) << 23 |
 // cell (< 4096) << 11 | index (< 2048) -- when the frame's keypoint capacity allows, else the 64-bit
-// form the resolution pass reads (dist << 32 | cell << 12 | index).
+// form the resolution pass reads (cand_key).
 template <typename K>
 __device__ __forceinline__ K scan_key(int dist, int cell, int i) {
   if constexpr (sizeof(K) == 4)
     return (uint32_t)dist << 23 | (uint32_t)cell << 11 | (uint32_t)i;
   else
-    return ((uint64_t)dist << 32) | ((uint64_t)cell << 12) | (uint64_t)i;
+    return cand_key(dist, cell, i);
 }
 template <typename K>
 __device__ __forceinline__ uint64_t key64(K k) {
   if constexpr (sizeof(K) == 4)
-    return k == ~0u ? kNoKey
-                    : ((uint64_t)(k >> 23) << 32) | ((uint64_t)((k >> 11) & 0xfffu) << 12) |
-                          (uint64_t)(k & 0x7ffu);
+    return k == ~0u ? kNoKey : cand_key(k >> 23, (int)((k >> 11) & 0xfffu), (int)(k & 0x7ffu));
   else
     return k;
 }
 
 // G lanes per query (the group of `lane`): 64 for the resolution pass's rescans, 16 for
 // search_cand (a window holds a handful of keypoints: four queries per wave keep the lanes busy)
-// float -> int of a cell coordinate with its argument held in range first: a float-to-int
-// conversion out of int's range (or of NaN) is undefined, so no coordinate reaches one
-__device__ __forceinline__ int cell_floor(float v) { return (int)floorf(fminf(fmaxf(v, -1e6f), 1e6f)); }
-__device__ __forceinline__ int cell_ceil(float v) { return (int)ceilf(fminf(fmaxf(v, -1e6f), 1e6f)); }
-
 // skip: the group has no query (or its context failed): it scans nothing -- no cell bound is
 // derived from its coordinates -- but still takes part in the group's shuffles and the merge
 template <typename K, int G = 64>
@@ -904,18 +814,15 @@ __device__ int scan_query_k(const ScanCtx& c, const Camera& cam, const FrameView
                             const uint32_t* claimed, uint64_t* top, int lane, bool skip = false) {
   const int gl = lane & (G - 1), gb = lane & ~(G - 1);
   int nMinCellX = 0, nMaxCellX = -1, nMinCellY = 0, nMaxCellY = -1;  // empty window
-  if (!skip) {
-    nMinCellX = max(0, cell_floor((c.x - cam.min_x - c.r) / cam.cell_w));
-    nMaxCellX = min(kGridCols - 1, cell_ceil((c.x - cam.min_x + c.r) / cam.cell_w));
-    nMinCellY = max(0, cell_floor((c.y - cam.min_y - c.r) / cam.cell_h));
-    nMaxCellY = min(kGridRows - 1, cell_ceil((c.y - cam.min_y + c.r) / cam.cell_h));
-  }
+  if (!skip)
+    cell_window(c.x, c.y, c.r, cam.min_x, cam.min_y, cam.cell_w, cam.cell_h, &nMinCellX,
+                &nMaxCellX, &nMinCellY, &nMaxCellY);
   constexpr K kNone = (K)~(K)0;
   K t[kTopK];
 #pragma unroll
   for (int k = 0; k < kTopK; k++) t[k] = kNone;
   int cnt = 0;
-  if (!(nMaxCellX < 0 || nMinCellX >= kGridCols || nMaxCellY < 0 || nMinCellY >= kGridRows)) {
+  if (window_on_grid(nMinCellX, nMaxCellX, nMinCellY, nMaxCellY)) {
     const bool bCheckLevels = (c.min_level > 0) || (c.max_level >= 0);
     const int ny = nMaxCellY - nMinCellY + 1;
     const int total = (nMaxCellX - nMinCellX + 1) * ny;
@@ -987,7 +894,7 @@ __device__ int scan_query_k(const ScanCtx& c, const Camera& cam, const FrameView
   for (int k = 0; k < kTopK; k++) top[k] = kNoKey;
 #pragma unroll
   for (int k = 0; k < kTopK; k++) {
-    const K m = G == 64 ? wave_min_key(t[0]) : group_min_key<G>(t[0]);
+    const K m = group_min_key<G>(t[0]);
     if (G == 64) {
       if (m == kNone) break;  // wave-uniform
     } else if (__ballot(m != kNone) == 0) {
@@ -1002,7 +909,7 @@ __device__ int scan_query_k(const ScanCtx& c, const Camera& cam, const FrameView
       top[k] = key64<K>(m);
     }
   }
-  return G == 64 ? wave_sum_bfly(cnt) : group_sum<G>(cnt);
+  return group_sum<G>(cnt);
 }
 
 // 32-bit keys whenever the frame's keypoint indices fit 11 bits (kp_cap <= 2048: nfeatures up to
@@ -1015,21 +922,12 @@ __device__ __forceinline__ int scan_query(const ScanCtx& c, const Camera& cam, c
   return scan_query_k<uint64_t, G>(c, cam, F, claimed, top, lane, skip);
 }
 
-__device__ __forceinline__ int key_idx(uint64_t k) { return (int)(k & 0xfff); }
-__device__ __forceinline__ int key_dist(uint64_t k) { return (int)(k >> 32); }
-
-// OpenCV small float gemm d = A*b + c (matmul.cpp, len 3): float dot, then (float)((double)+).
-__device__ __forceinline__ float mat3_row(const float* R, int r, const float* x, float c) {
-  const float dot = R[3 * r] * x[0] + R[3 * r + 1] * x[1] + R[3 * r + 2] * x[2];
-  return (float)((double)dot + (double)c);
-}
-
 // SearchByProjection(CurrentFrame, LastFrame) per-query setup (orb_matcher.cpp:1336-1376).
 __device__ bool f2f_ctx(const F2FQuery& q, const F2FPose& P, const Camera& cam,
                         const OrbGeom* g, ScanCtx* c) {
-  const float xc = mat3_row(P.Rcw, 0, q.xyz, P.tcw[0]);
-  const float yc = mat3_row(P.Rcw, 1, q.xyz, P.tcw[1]);
-  const float zc = mat3_row(P.Rcw, 2, q.xyz, P.tcw[2]);
+  const float xc = gemm_row(P.Rcw, q.xyz, P.tcw[0]);
+  const float yc = gemm_row(P.Rcw + 3, q.xyz, P.tcw[1]);
+  const float zc = gemm_row(P.Rcw + 6, q.xyz, P.tcw[2]);
   const float invzc = (float)(1.0 / (double)zc);
   if (invzc < 0) return false;
   const float u = fmaf(cam.fx * xc, invzc, cam.cx);
@@ -1055,7 +953,7 @@ __device__ bool f2f_ctx(const F2FQuery& q, const F2FPose& P, const Camera& cam,
   }
   c->ur = fmaf(-cam.bf, invzc, u);
   c->gate = radius;
-  c->max_dist = TH_HIGH;  // a candidate above TH_HIGH can never become the accepted match
+  c->max_dist = kThHigh;  // a candidate above kThHigh can never become the accepted match
   c->desc = q.desc;
   return true;
 }
@@ -1078,15 +976,6 @@ __device__ bool mps_ctx(const MpsQuery& q, int th, const OrbGeom* g, ScanCtx* c)
   return true;
 }
 
-// cv::norm of a 3-vector: a double sum of squares, its sqrt rounded to float.
-__device__ __forceinline__ float norm3(float a, float b, float c) {
-  double s = 0.0;
-  s += (double)a * (double)a;
-  s += (double)b * (double)b;
-  s += (double)c * (double)c;
-  return (float)sqrt(s);
-}
-
 // SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) per-query setup
 // (orb_matcher.cpp:1473-1513; PredictScale map_point.cpp:382-396). No depth gate and no
 // right-coordinate gate; the octave window is level-1 .. level+1. Where the reference's
@@ -1095,9 +984,9 @@ __device__ __forceinline__ float norm3(float a, float b, float c) {
 __device__ bool reloc_ctx(const RelocQuery& q, const RelocPose& P, const Camera& cam,
                           const OrbGeom* g, ScanCtx* c) {
   if (q.skip) return false;
-  const float xc = mat3_row(P.Rcw, 0, q.xyz, P.tcw[0]);
-  const float yc = mat3_row(P.Rcw, 1, q.xyz, P.tcw[1]);
-  const float zc = mat3_row(P.Rcw, 2, q.xyz, P.tcw[2]);
+  const float xc = gemm_row(P.Rcw, q.xyz, P.tcw[0]);
+  const float yc = gemm_row(P.Rcw + 3, q.xyz, P.tcw[1]);
+  const float zc = gemm_row(P.Rcw + 6, q.xyz, P.tcw[2]);
   const float invzc = (float)(1.0 / (double)zc);
   const float u = fmaf(cam.fx * xc, invzc, cam.cx);
   const float v = fmaf(cam.fy * yc, invzc, cam.cy);
@@ -1109,8 +998,7 @@ __device__ bool reloc_ctx(const RelocQuery& q, const RelocPose& P, const Camera&
   if (dist3D < 0.8f * q.min_dist || dist3D > 1.2f * q.max_dist) return false;
   const float ratio = q.max_dist / dist3D;
   if (!isfinite(ratio) || !(ratio > 0.0f)) return false;
-  int level = (int)ceilf(glibc_logf(ratio) / g->log_scale_factor);
-  level = level < 0 ? 0 : (level >= g->nlevels ? g->nlevels - 1 : level);
+  const int level = predict_scale(q.max_dist, dist3D, g->log_scale_factor, g->nlevels);
   c->x = u;
   c->y = v;
   c->r = P.th * g->lv[level].scale;
@@ -1133,6 +1021,29 @@ struct SearchPose<RelocQuery> {
   using type = RelocPose;
 };
 
+// The per-query setup of the query type's overload.
+template <typename Q>
+__device__ __forceinline__ bool make_ctx(const Q& q, const typename SearchPose<Q>::type* poses,
+                                         int f, int th, const Camera& cam, const OrbGeom* g,
+                                         ScanCtx* c) {
+  if constexpr (std::is_same<Q, F2FQuery>::value) return f2f_ctx(q, poses[f], cam, g, c);
+  else if constexpr (std::is_same<Q, RelocQuery>::value) return reloc_ctx(q, poses[f], cam, g, c);
+  else return mps_ctx(q, th, g, c);
+}
+
+__device__ __forceinline__ FrameView frame_view(int f, const FrameKps& cur, const float* u_right,
+                                                int64_t ur_stride, const GridWorkspace& gw,
+                                                const MatchIO& io, int kp_cap) {
+  FrameView F;
+  F.kps = cur.kps + f * cur.stride;
+  F.desc = cur.desc + f * cur.stride * 32;
+  F.u_right = u_right + f * ur_stride;
+  F.cell_start = gw.cell_start + (int64_t)f * (kGridCells + 1);
+  F.cell_items = gw.cell_items + (int64_t)f * kp_cap;
+  F.blocked = io.blocked + f * io.mp_stride;
+  return F;
+}
+
 #ifndef SEARCH_LANES
 #define SEARCH_LANES 16
 #endif
@@ -1152,23 +1063,9 @@ __global__ __launch_bounds__(256) void search_cand_kernel(
   if (__builtin_amdgcn_readfirstlane((bx * 4 + wave_id()) * (64 / kSearchG)) >= qcount) return;
   const bool live = qi < qcount;  // the wave's last groups may have no query
   const int q = io.q_start[f] + (live ? qi : 0);
-  FrameView F;
-  F.kps = cur.kps + f * cur.stride;
-  F.desc = cur.desc + f * cur.stride * 32;
-  F.u_right = u_right + f * ur_stride;
-  F.cell_start = gw.cell_start + (int64_t)f * (kGridCells + 1);
-  F.cell_items = gw.cell_items + (int64_t)f * g->kp_cap;
-  F.blocked = io.blocked + f * io.mp_stride;
+  const FrameView F = frame_view(f, cur, u_right, ur_stride, gw, io, g->kp_cap);
   ScanCtx c;
-  bool ok;
-  if constexpr (std::is_same<Q, F2FQuery>::value) {
-    ok = f2f_ctx(queries[q], poses[f], cam, g, &c);
-  } else if constexpr (std::is_same<Q, RelocQuery>::value) {
-    ok = reloc_ctx(queries[q], poses[f], cam, g, &c);
-  } else {
-    ok = mps_ctx(queries[q], th, g, &c);
-  }
-  ok = ok && live;
+  const bool ok = make_ctx(queries[q], poses, f, th, cam, g, &c) && live;
   uint64_t top[kTopK];
   // a group without a query scans nothing but takes part in the merge
   const int n = scan_query<kSearchG>(c, cam, F, nullptr, top, lane, g->kp_cap, !ok);
@@ -1200,9 +1097,9 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
   // kept candidates are all <= ORBdist (reloc_ctx), so any kept candidate is accepted
   constexpr bool kReloc = std::is_same<Q, RelocQuery>::value;
   constexpr bool kF2F = std::is_same<Q, F2FQuery>::value || kReloc;
-  constexpr int kAccept = kReloc ? 256 : TH_HIGH;
+  constexpr int kAccept = kReloc ? 256 : kThHigh;
   __shared__ uint32_t claimed[128];  // kp_cap <= 4096
-  __shared__ int hist[HISTO_LENGTH];
+  __shared__ int hist[kHisto];
   __shared__ float s_kang[kF2F ? 4096 : 1];
   __shared__ int8_t s_koct[kF2F ? 1 : 4096];
   __shared__ int owner[4096];
@@ -1212,14 +1109,8 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
   const int lane = threadIdx.x;
   const int n = cur.n[f * cur.n_stride];
   for (int i = lane; i < 128; i += 64) claimed[i] = 0;
-  if (lane < HISTO_LENGTH) hist[lane] = 0;
-  FrameView F;
-  F.kps = cur.kps + f * cur.stride;
-  F.desc = cur.desc + f * cur.stride * 32;
-  F.u_right = u_right + f * ur_stride;
-  F.cell_start = gw.cell_start + (int64_t)f * (kGridCells + 1);
-  F.cell_items = gw.cell_items + (int64_t)f * g->kp_cap;
-  F.blocked = io.blocked + f * io.mp_stride;
+  if (lane < kHisto) hist[lane] = 0;
+  const FrameView F = frame_view(f, cur, u_right, ur_stride, gw, io, g->kp_cap);
   int* mp = io.map_point + f * io.mp_stride;
   uint8_t* blk = io.blocked + f * io.mp_stride;
   bool check_ori = false;
@@ -1267,6 +1158,20 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
   __builtin_amdgcn_wave_barrier();
   const int need = kF2F ? 1 : 2;
   auto is_claimed = [&](int idx) { return (claimed[idx >> 5] >> (idx & 31)) & 1u; };
+  // acceptance of a query's best candidate b1 (a candidate, not kNoKey) given its second b2 (F2F:
+  // the distance gate; local map: + the ratio test between candidates of one level, :76-99)
+  auto accepts = [&](uint64_t b1, uint64_t b2) {
+    bool acc = key_dist(b1) <= kAccept;
+    if constexpr (!kF2F) {
+      if (acc) {
+        const int lv1 = s_koct[key_idx(b1)];
+        const int d2 = b2 == kNoKey ? 256 : key_dist(b2);
+        const int lv2 = b2 == kNoKey ? -1 : s_koct[key_idx(b2)];
+        if (lv1 == lv2 && (float)key_dist(b1) > nnratio * (float)d2) acc = false;
+      }
+    }
+    return acc;
+  };
   // one lane's query of a chunk: its kept candidates, candidate count, map point word, angle
   struct QIn {
     uint64_t key[kTopK];
@@ -1311,7 +1216,6 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
   for (int c0 = 0; c0 < qn; c0 += 64) {
     const int qi = c0 + lane;
     const bool valid = qi < qn;
-    const int q = q0 + qi;
     const QIn in = nx;
     if (c0 + 64 < qn) load_chunk(c0 + 64, nx);  // in flight while this chunk resolves
     const uint64_t* key = in.key;
@@ -1347,15 +1251,7 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
           navail++;
         }
         // accepted blocking choice -> owner (the lowest such lane wins the keypoint)
-        bool acc = b1 != kNoKey && key_dist(b1) <= kAccept;
-        if constexpr (!kF2F) {
-          if (acc) {
-            const int lv1 = s_koct[key_idx(b1)];
-            const int d2 = b2 == kNoKey ? 256 : key_dist(b2);
-            const int lv2 = b2 == kNoKey ? -1 : s_koct[key_idx(b2)];
-            if (lv1 == lv2 && (float)key_dist(b1) > nnratio * (float)d2) acc = false;
-          }
-        }
+        const bool acc = b1 != kNoKey && accepts(b1, b2);
         mine = (act && acc && qblocks) ? key_idx(b1) : -1;
         if (!__ballot(mine != prev)) break;
         if (prev >= 0) owner[prev] = INT_MAX;
@@ -1373,17 +1269,8 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
       __builtin_amdgcn_wave_barrier();
       auto commit = [&](bool doit, uint64_t c1, uint64_t c2) {
-        // acceptance (F2F: distance gate; local map: + ratio test, :76-99)
         const bool touched = doit && c1 != kNoKey;
-        bool acc = touched && key_dist(c1) <= kAccept;
-        if constexpr (!kF2F) {
-          if (acc) {
-            const int lv1 = s_koct[key_idx(c1)];
-            const int d2 = c2 == kNoKey ? 256 : key_dist(c2);
-            const int lv2 = c2 == kNoKey ? -1 : s_koct[key_idx(c2)];
-            if (lv1 == lv2 && (float)key_dist(c1) > nnratio * (float)d2) acc = false;
-          }
-        }
+        const bool acc = touched && accepts(c1, c2);
         const int idx = touched ? key_idx(c1) : 0;
         nm += __popcll(__ballot(acc));
         // last writer (highest lane) of each keypoint sets mp / blocked
@@ -1400,11 +1287,7 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
         if (acc && qblocks) atomicOr(&claimed[idx >> 5], 1u << (idx & 31));
         if constexpr (kF2F) {
           if (acc && check_ori) {
-            float rot = qang - s_kang[idx];
-            if (rot < 0.0f) rot += 360.0f;
-            const float factor = 1.0f / HISTO_LENGTH;
-            int bin = (int)roundf(rot * factor);
-            if (bin == HISTO_LENGTH) bin = 0;
+            const int bin = rot_bin(qang, s_kang[idx]);
             set_bin(qi, bin, idx);
             atomicAdd(&hist[bin], 1);
           }
@@ -1419,11 +1302,7 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
       if (r < 64 && c0 + r < qn) {
         // lane r: every kept candidate is taken -> rescan its window with the live claims
         ScanCtx c;
-        bool okc;
-        const int qr = q0 + c0 + r;
-        if constexpr (kReloc) okc = reloc_ctx(queries[qr], poses[f], cam, g, &c);
-        else if constexpr (kF2F) okc = f2f_ctx(queries[qr], poses[f], cam, g, &c);
-        else okc = mps_ctx(queries[qr], th, g, &c);
+        const bool okc = make_ctx(queries[q0 + c0 + r], poses, f, th, cam, g, &c);
         uint64_t top[kTopK];
         if (okc) scan_query(c, cam, F, claimed, top, lane, g->kp_cap);
         const uint64_t t1 = __shfl(okc ? top[0] : kNoKey, 0, 64);
@@ -1432,33 +1311,13 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
       }
       start = r + 1;
     }
-    (void)q;
   }
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
   if constexpr (kF2F) {
     if (check_ori) {
-      // ComputeThreeMaxima (orb_matcher.cpp:1584-1625)
-      int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-      for (int i = 0; i < HISTO_LENGTH; i++) {
-        const int s = hist[i];
-        if (s > max1) {
-          max3 = max2; max2 = max1; max1 = s;
-          ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (s > max2) {
-          max3 = max2; max2 = s;
-          ind3 = ind2; ind2 = i;
-        } else if (s > max3) {
-          max3 = s;
-          ind3 = i;
-        }
-      }
-      if (max2 < 0.1f * (float)max1) {
-        ind2 = -1;
-        ind3 = -1;
-      } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-      }
+      int ind1, ind2, ind3;
+      three_maxima(hist, &ind1, &ind2, &ind3);
       // SetMapPoint(rotHist[i][j], nullptr) for every entry of a rejected bin (:1441-1450)
       int removed = 0;
       for (int qi = lane; qi < qn; qi += 64) {
@@ -1474,46 +1333,47 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
       nm -= wave_sum(removed);
     }
   }
-  (void)n;
   if (lane == 0) io.nmatches[f] = nm;
+}
+
+// The candidate search of every frame's queries, then the in-order claim resolution.
+template <typename Q>
+static void launch_search(const FrameKps& cur, const float* u_right, int64_t ur_stride,
+                          const Camera& cam, const OrbGeomDev& g, const Q* queries,
+                          const typename SearchPose<Q>::type* poses, int th, float nnratio,
+                          int n_frames, int max_q, const GridWorkspace& gw,
+                          const MatchWorkspace& mw, const MatchIO& io, hipStream_t st) {
+  constexpr int kPerBlock = 4 * (64 / kSearchG);  // queries per work-group of search_cand
+  if (max_q > 0)
+    SLAMGPU_LAUNCH("search_cand", st, search_cand_kernel<Q>,
+                   dim3((max_q + kPerBlock - 1) / kPerBlock, n_frames), dim3(256), 0, st, cur,
+                   u_right, ur_stride, cam, g.dev, queries, poses, th, gw, mw, io);
+  SLAMGPU_LAUNCH("search_resolve", st, search_resolve_kernel<Q>, dim3(n_frames), dim3(64), 0, st,
+                 cur, u_right, ur_stride, cam, g.dev, queries, poses, th, nnratio, gw, mw, io);
 }
 
 void launch_search_frame(const FrameKps& cur, const float* u_right, int64_t ur_stride,
                          const Camera& cam, const OrbGeomDev& g, const F2FQuery* queries,
                          const F2FPose* poses, int n_frames, int max_q, const GridWorkspace& gw,
                          const MatchWorkspace& mw, const MatchIO& io, hipStream_t st) {
-  if (max_q > 0)
-    SLAMGPU_LAUNCH("search_cand", st, search_cand_kernel<F2FQuery>,
-                   dim3((max_q + 4 * (64 / kSearchG) - 1) / (4 * (64 / kSearchG)), n_frames), dim3(256),
-                       0, st, cur, u_right, ur_stride, cam, g.dev, queries, poses, 0, gw, mw, io);
-  SLAMGPU_LAUNCH("search_resolve", st, search_resolve_kernel<F2FQuery>, dim3(n_frames), dim3(64), 0, st, cur,
-                     u_right, ur_stride, cam, g.dev, queries, poses, 0, 0.0f, gw, mw, io);
+  launch_search(cur, u_right, ur_stride, cam, g, queries, poses, 0, 0.0f, n_frames, max_q, gw, mw,
+                io, st);
 }
 
 void launch_search_mps(const FrameKps& cur, const float* u_right, int64_t ur_stride,
                        const Camera& cam, const OrbGeomDev& g, const MpsQuery* queries,
                        float nnratio, int th, int n_frames, int max_q, const GridWorkspace& gw,
                        const MatchWorkspace& mw, const MatchIO& io, hipStream_t st) {
-  if (max_q > 0)
-    SLAMGPU_LAUNCH("search_cand", st, search_cand_kernel<MpsQuery>,
-                   dim3((max_q + 4 * (64 / kSearchG) - 1) / (4 * (64 / kSearchG)), n_frames), dim3(256),
-                       0, st, cur, u_right, ur_stride, cam, g.dev, queries,
-                       (const F2FPose*)nullptr, th, gw, mw, io);
-  SLAMGPU_LAUNCH("search_resolve", st, search_resolve_kernel<MpsQuery>, dim3(n_frames), dim3(64), 0, st, cur,
-                     u_right, ur_stride, cam, g.dev, queries, (const F2FPose*)nullptr, th,
-                     nnratio, gw, mw, io);
+  launch_search(cur, u_right, ur_stride, cam, g, queries, (const F2FPose*)nullptr, th, nnratio,
+                n_frames, max_q, gw, mw, io, st);
 }
 
 void launch_search_reloc(const FrameKps& cur, const float* u_right, int64_t ur_stride,
                          const Camera& cam, const OrbGeomDev& g, const RelocQuery* queries,
                          const RelocPose* poses, int n_frames, int max_q, const GridWorkspace& gw,
                          const MatchWorkspace& mw, const MatchIO& io, hipStream_t st) {
-  if (max_q > 0)
-    SLAMGPU_LAUNCH("search_cand", st, search_cand_kernel<RelocQuery>,
-                   dim3((max_q + 4 * (64 / kSearchG) - 1) / (4 * (64 / kSearchG)), n_frames), dim3(256),
-                       0, st, cur, u_right, ur_stride, cam, g.dev, queries, poses, 0, gw, mw, io);
-  SLAMGPU_LAUNCH("search_resolve", st, search_resolve_kernel<RelocQuery>, dim3(n_frames), dim3(64), 0, st, cur,
-                     u_right, ur_stride, cam, g.dev, queries, poses, 0, 0.0f, gw, mw, io);
+  launch_search(cur, u_right, ur_stride, cam, g, queries, poses, 0, 0.0f, n_frames, max_q, gw, mw,
+                io, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1570,7 +1430,7 @@ __global__ __launch_bounds__(256) void vo_queries_kernel(FrameKps src, const flo
       const float y = (kp.y - cam.cy) * zz * invfy;
       F2FQuery q;
       const float xc[3] = {x, y, zz};
-      for (int r = 0; r < 3; r++) q.xyz[r] = mat3_row(Rwc, r, xc, Ow[r]);
+      for (int r = 0; r < 3; r++) q.xyz[r] = gemm_row(Rwc + 3 * r, xc, Ow[r]);
       q.last_angle = kp.angle;
       q.last_octave = kp.octave;
       q.mp_id = i;

@@ -46,9 +46,10 @@ In the keyframe matchers' cases the families window .. off_grid share one case, 
   histogram         x      -      -          -         -           x      -     x
   check_ori_off     x      -      -          -         -           x      -     x
 
-SearchByBoW (entry "bow"; its tie order is constructed in test_bow_gpu.py) has two cases here: the
-threshold's strictness in its two overloads (<= TH_LOW :202, < TH_LOW :575) and the ratio test at
-equality, a tied minimum and a keypoint already taken (:186-204).
+SearchByBoW (entry "bow"; its tie order is constructed in test_bow_gpu.py) has the threshold's
+strictness in its two overloads (<= TH_LOW :202, < TH_LOW :575), the ratio test at equality, a tied
+minimum and a keypoint already taken (:186-204), and the histogram and check_ori_off families of
+SearchForTriangulation on the same keyframes and angle sets (:210-220, :241-259).
 
 (a) SearchBySim3 claims nothing; its vbAlreadyMatched flags are in its threshold case.
 (b) with the forward and the backward window (:1371-1376).
@@ -882,7 +883,10 @@ def hist_plans():
     return plans
 
 
-def _tri_hist_cases(seed):
+def _tri_hist_cases(seed, entry="tri", cite_off=":750", **extra):
+    """The rotation-histogram plans as SearchForTriangulation pairs; with entry "bow" (and extra =
+    its kf_kf and nnratio) the same keyframes, angle sets and expectations through SearchByBoW:
+    every match is at distance 10 with no second candidate below 90."""
     out = []
     for name, (rots, exp, alt) in hist_plans().items():
         n1 = len(rots)
@@ -898,12 +902,12 @@ def _tri_hist_cases(seed):
         a = [i if k else -1 for i, k in enumerate(alt)]
         des = [i for i in range(n1) if e[i] != a[i]]
         sup = {i: e[i] for i in range(n1) if e[i] == a[i]}
-        out.append(Case("tri", "histogram", name, ":1584-1625", T.inp(check_ori=True), des,
-                        [e[i] for i in des], [a[i] for i in des], "match12", support=sup))
+        out.append(Case(entry, "histogram", name, ":1584-1625", dict(T.inp(check_ori=True), **extra),
+                        des, [e[i] for i in des], [a[i] for i in des], "match12", support=sup))
         if name == "edges":
-            inp = dict(T.inp(), check_ori=False)
+            inp = dict(T.inp(), check_ori=False, **extra)
             des = [i for i in range(n1) if e[i] < 0]
-            out.append(Case("tri", "check_ori_off", name, ":750", inp, des, des,
+            out.append(Case(entry, "check_ori_off", name, cite_off, inp, des, des,
                             [-1] * len(des), "match12",
                             support={i: i for i in range(n1) if e[i] >= 0}))
     return out
@@ -953,6 +957,9 @@ def _bow_cases(seed):
     inp = dict(T.inp(), kf_kf=False, nnratio=0.8)
     out.append(Case("bow", "ratio", "nn08", ":204/:186", inp, [0, 2, 4], [-1, -1, 77],
                     [10, 12, 13], "match12", support={1: 11, 3: 13}))
+    # the rotation histogram (:210-220 bins, :241-259 removal) on the triangulation cases' angle
+    # sets, and the same matches with mbCheckOrientation off
+    out += _tri_hist_cases(seed + 2, "bow", ":241", kf_kf=False, nnratio=0.6)
     return out
 
 
@@ -1591,7 +1598,7 @@ KF_FAMILIES = {
     "fuse_sim3": ("tie", "threshold", "gates"),
     "sbp_sim3": ("tie", "threshold", "gates", "claims"),
     "sim3": ("tie", "threshold", "gates"),
-    "bow": ("threshold", "ratio")}
+    "bow": ("threshold", "ratio", "histogram", "check_ori_off")}
 KF_CASE_IDS = ("fuse-threshold-best_dist", "fuse_sim3-threshold-best_dist", "tri-tie-one_node",
                "tri-tie-three_nodes", "bow-threshold-frame_le", "bow-threshold-kf_kf_lt")
 FRAME_FAMILIES = {

@@ -5,7 +5,7 @@ tests/test_match_boundaries.py holds to the expectations written down from orb_m
 case runs through the single call of its entry point, and once through the batched device form of
 each of the eight entry points with all its cases in one launch (one launch per window factor,
 check_ori setting or nnratio where that is a launch parameter): the batch neighbours are then
-boundary cases too. SearchByBoW's two cases run through its single call only."""
+boundary cases too. SearchByBoW's cases run through its single call only."""
 import numpy as np
 import pytest
 
