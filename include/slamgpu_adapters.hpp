@@ -26,6 +26,7 @@
 
 #include "slamgpu.h"
 #include "slamgpu_bow.h"
+#include "slamgpu_initializer.h"
 #include "slamgpu_kfmatch.h"
 #include "slamgpu_loopmatch.h"
 #include "slamgpu_optimizer.h"
@@ -1316,6 +1317,125 @@ class PnPSolverCore {
   std::vector<int32_t> draws_, events_;
   std::vector<slamgpu_pnp_hyp> hyp_, refined_;
   std::vector<uint64_t> bits_, refined_bits_;
+};
+
+// ---- Monocular Initializer (include/slamgpu_initializer.h) --------------------------------------
+
+// DUtils::Random::SeedRandOnce(int) (DUtils/Random.cpp:38-45): srand(seed) the first time in the
+// process.
+inline void seed_rand_once(int seed) {
+  static bool already_seeded = false;
+  if (!already_seeded) {
+    std::srand(seed);
+    already_seeded = true;
+  }
+}
+
+// The reference's Initializer (src/util/initializer.h) over plain arrays: keys = the undistorted
+// keypoint positions (x, y) of a frame. Initialize draws the schedule as initializer.cpp:60-77
+// does (SeedRandOnce(0), then eight RandomInt per iteration), makes the ONE synchronous device call
+// and replays :92-98 and the tails of ReconstructH (:693-735) / ReconstructF (:495-565) from its
+// outputs. R21 (3x3 row-major), t21, vP3D ([n1][3]) and vbTriangulated are written only when it
+// returns true, as the reference's are.
+class InitializerCore {
+ public:
+  using RandomInt = std::function<int(int, int)>;
+
+  InitializerCore(const float* keys1, int n1, const float K[4], float sigma = 1.0f,
+                  int iterations = 200, RandomInt random_int = reference_random_int)
+      : keys1_(keys1, keys1 + 2 * (size_t)n1), n1_(n1), sigma_(sigma), iterations_(iterations),
+        random_int_(std::move(random_int)) {
+    std::memcpy(K_, K, sizeof K_);
+  }
+
+  bool Initialize(const float* keys2, int n2, const std::vector<int>& vMatches12, float R21[9],
+                  float t21[3], std::vector<float>& vP3D, std::vector<bool>& vbTriangulated,
+                  float minParallax = 1.0f, int minTriangulated = 50) {
+    if ((int)vMatches12.size() != n1_)
+      throw std::runtime_error("slamgpu: Initializer: one vMatches12 entry per key of frame 1");
+    std::vector<int32_t> m12(vMatches12.begin(), vMatches12.end());
+    int N = 0;
+    for (int m : m12) N += m >= 0;
+    seed_rand_once(0);
+    draws_.clear();
+    for (int it = 0; it < iterations_; ++it)
+      for (int j = 0; j < 8; ++j) draws_.push_back(random_int_(0, N - 1 - j));
+    const size_t words = SLAMGPU_INIT_MASK_WORDS(n1_), its = (size_t)std::max(iterations_, 1);
+    hyp_.assign(2 * its, slamgpu_init_hyp{});
+    bits_.assign(2 * its * words, 0);
+    std::vector<int32_t> pairs(2 * (size_t)n1_);
+    std::vector<uint64_t> good(SLAMGPU_INIT_MAX_MOTIONS * words);
+    std::vector<float> p3d((size_t)SLAMGPU_INIT_MAX_MOTIONS * 3 * n1_);
+    ++device_calls_;
+    throw_if(slamgpu_init_ransac(keys1_.data(), m12.data(), n1_, keys2, n2, K_, sigma_,
+                                 draws_.data(), iterations_, hyp_.data(), bits_.data(), &result_,
+                                 pairs.data(), motion_, good.data(), p3d.data()),
+             slamgpu_initializer_last_error);
+    const int model = result_.model, nm = result_.n_motions, b = result_.best[model];
+    if (b < 0 || nm == 0) return false;  // an empty mask (:160), or the early return of :601
+    const uint64_t* hb = &bits_[((size_t)model * iterations_ + b) * words];
+    int Nin = 0;
+    for (int i = 0; i < result_.n; ++i) Nin += (int)(hb[i / 64] >> (i % 64) & 1);
+    float parallax[SLAMGPU_INIT_MAX_MOTIONS];
+    for (int i = 0; i < nm; ++i)
+      parallax[i] = motion_[i].n_good > 0
+                        ? (float)(std::acos((double)motion_[i].cos_parallax) * 180 /
+                                  3.1415926535897932384626433832795)
+                        : 0.0f;
+    int chosen = -1;
+    if (model == SLAMGPU_INIT_MODEL_F) {
+      int maxGood = 0, nsimilar = 0;
+      for (int i = 0; i < 4; ++i) maxGood = std::max(maxGood, motion_[i].n_good);
+      const int nMinGood = std::max(static_cast<int>(0.9 * Nin), minTriangulated);
+      for (int i = 0; i < 4; ++i)
+        if (motion_[i].n_good > 0.7 * maxGood) nsimilar++;
+      if (maxGood < nMinGood || nsimilar > 1) return false;
+      for (int i = 0; i < 4 && chosen < 0; ++i)
+        if (maxGood == motion_[i].n_good) chosen = i;  // the else-if chain: the first that ties
+      if (!(parallax[chosen] > minParallax)) return false;
+    } else {
+      int bestGood = 0, secondBestGood = 0;
+      float bestParallax = -1;
+      for (int i = 0; i < nm; ++i) {
+        const int nGood = motion_[i].n_good;
+        if (nGood > bestGood) {
+          secondBestGood = bestGood;
+          bestGood = nGood;
+          chosen = i;
+          bestParallax = parallax[i];
+        } else if (nGood > secondBestGood) {
+          secondBestGood = nGood;
+        }
+      }
+      if (!(secondBestGood < 0.75 * bestGood && bestParallax >= minParallax &&
+            bestGood > minTriangulated && bestGood > 0.9 * Nin))
+        return false;
+    }
+    std::memcpy(R21, motion_[chosen].R, sizeof motion_[chosen].R);
+    std::memcpy(t21, motion_[chosen].t, sizeof motion_[chosen].t);
+    vP3D.assign(p3d.begin() + (size_t)chosen * 3 * n1_, p3d.begin() + (size_t)(chosen + 1) * 3 * n1_);
+    vbTriangulated.assign(n1_, false);
+    for (int i = 0; i < n1_; ++i)
+      if (good[(size_t)chosen * words + i / 64] >> (i % 64) & 1) vbTriangulated[i] = true;
+    return true;
+  }
+
+  const slamgpu_init_result& result() const { return result_; }  // of the last Initialize
+  const std::vector<int32_t>& draws() const { return draws_; }
+  int device_calls() const { return device_calls_; }
+
+ private:
+  std::vector<float> keys1_;
+  int n1_;
+  float K_[4], sigma_;
+  int iterations_;
+  RandomInt random_int_;
+  std::vector<int32_t> draws_;
+  std::vector<slamgpu_init_hyp> hyp_;
+  std::vector<uint64_t> bits_;
+  slamgpu_init_result result_{};
+  slamgpu_init_motion motion_[SLAMGPU_INIT_MAX_MOTIONS] = {};
+  int device_calls_ = 0;
 };
 
 // ---- Optimizer::BundleAdjustment (optimizer.cpp:33-207), GlobalBundleAdjustemnt (:18-31) ----

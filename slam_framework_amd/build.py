@@ -42,6 +42,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_host_stage_check()
         build_sim3solver_adapter_check()
         build_pnpsolver_adapter_check()
+        build_initializer_adapter_check()
         build_reloc_adapter_check()
         build_device_math_check()
         return LIB
@@ -74,6 +75,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_host_stage_check()
     build_sim3solver_adapter_check()
     build_pnpsolver_adapter_check()
+    build_initializer_adapter_check()
     build_reloc_adapter_check()
     build_device_math_check()
     return LIB
@@ -154,6 +156,25 @@ def build_pnpsolver_adapter_check() -> str:
                     "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", PNPSOLVER_ADAPTER_BIN],
                    check=True)
     return PNPSOLVER_ADAPTER_BIN
+
+
+INITIALIZER_ADAPTER_SRC = os.path.join(ROOT, "tests", "initializer_adapter_check.cpp")
+INITIALIZER_ADAPTER_BIN = os.path.join(ROOT, "tests", "initializer_adapter_check")
+
+
+def build_initializer_adapter_check() -> str:
+    """g++ build of tests/initializer_adapter_check.cpp: InitializerCore of
+    include/slamgpu_adapters.hpp (the eager draws after SeedRandOnce(0), the one device call, the
+    replay of the ReconstructH / ReconstructF tails) driven from C++ against libslamgpu.so."""
+    deps = [INITIALIZER_ADAPTER_SRC, LIB] + glob.glob(os.path.join(ROOT, "include", "*.h*"))
+    if os.path.exists(INITIALIZER_ADAPTER_BIN) and os.path.getmtime(INITIALIZER_ADAPTER_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return INITIALIZER_ADAPTER_BIN
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I",
+                    os.path.join(ROOT, "include"), INITIALIZER_ADAPTER_SRC, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", INITIALIZER_ADAPTER_BIN],
+                   check=True)
+    return INITIALIZER_ADAPTER_BIN
 
 
 RELOC_ADAPTER_SRC = os.path.join(ROOT, "tests", "reloc_adapter_check.cpp")

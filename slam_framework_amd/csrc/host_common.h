@@ -38,6 +38,7 @@ extern thread_local ErrorSlot t_bow_err;     // slamgpu_bow_last_error
 extern thread_local ErrorSlot t_kf_err;      // slamgpu_kfmatch_last_error == slamgpu_loopmatch_last_error
 extern thread_local ErrorSlot t_s3_err;      // slamgpu_sim3solver_last_error
 extern thread_local ErrorSlot t_pnp_err;     // slamgpu_pnpsolver_last_error
+extern thread_local ErrorSlot t_init_err;    // slamgpu_initializer_last_error
 extern thread_local ErrorSlot t_io_err;      // slamgpu_io_last_error
 extern thread_local ErrorSlot t_create_err;  // slamgpu_last_error(NULL): why slamgpu_create failed
 

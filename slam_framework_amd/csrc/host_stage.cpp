@@ -9,6 +9,7 @@ thread_local ErrorSlot t_bow_err;
 thread_local ErrorSlot t_kf_err;
 thread_local ErrorSlot t_s3_err;
 thread_local ErrorSlot t_pnp_err;
+thread_local ErrorSlot t_init_err;
 thread_local ErrorSlot t_io_err;
 thread_local ErrorSlot t_create_err;
 

@@ -39,6 +39,7 @@
 #include "../../include/slamgpu_pnpsolver.h"
 #include "device_math.h"
 #include "host_stage.h"
+#include "jacobi_svd.h"
 #include "stage_layout.h"
 
 namespace slamgpu {
@@ -46,7 +47,6 @@ namespace {
 
 constexpr int kSweeps = 15;   // tools/pnp_jacobi_sweeps.py settles after 13, plus two
 constexpr int kMtmSums = 78;  // upper triangle of the 12 x 12 MtM
-constexpr int kPairLanes = 10;  // lanes per column pair: the 6 pairs of a 12-column round fit a wave
 
 struct PnpParams {
   double fu, fv, uc, vc;
@@ -109,73 +109,7 @@ __device__ __forceinline__ void wave_sum(WaveLds& S, const double (&part)[K], do
   for (int e = 0; e < K; e++) tot[e] = S.tot[e];
 }
 
-// ---- the one SVD -------------------------------------------------------------------------------
-
-// S.A (M x N, row-major) becomes A V with mutually orthogonal columns, S.V the rotations' product;
-// d[N] the column norms descending (ties: lower column first), ord[k] the column of d[k]. Right
-// singular vector k is column ord[k] of S.V, left singular vector k column ord[k] of S.A over d[k].
-template <int M, int N>
-__device__ __noinline__ void svd_lds(WaveLds& S, int lane, double* d, int* ord) {
-  for (int t = lane; t < N * N; t += 64) S.V[t] = (t / N == t % N) ? 1.0 : 0.0;
-  __syncthreads();
-  // Round-robin order (tests/pnpsolver_ref.c: jacobi_columns): the pairs of a round share no
-  // column, so group g of kPairLanes lanes takes pair g -- the dot products redundantly on each
-  // of its lanes, then the M rows of A and the N rows of V dealt over them.
-  constexpr int NP = N + (N & 1);
-  const int g = lane / kPairLanes, gl = lane % kPairLanes;
-#pragma unroll 1
-  for (int sw = 0; sw < kSweeps; sw++)
-#pragma unroll 1
-    for (int round = 0; round < NP - 1; round++) {
-      const int a = g == 0 ? NP - 1 : (round + g) % (NP - 1);
-      const int b = g == 0 ? round : (round - g + NP - 1) % (NP - 1);
-      const int p = a < b ? a : b, q = a < b ? b : a;
-      bool rot = false;
-      double c = 1.0, s = 0.0;
-      if (g < NP / 2 && q < N) {  // q >= N: the bye
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-#pragma unroll
-        for (int r = 0; r < M; r++) {
-          const double ap = S.A[r * N + p], aq = S.A[r * N + q];
-          alpha += ap * ap;
-          beta += aq * aq;
-          gamma += ap * aq;
-        }
-        rot = __builtin_fabs(gamma) > 1e-15 * __builtin_sqrt(alpha * beta);
-        if (rot) {
-          const double zeta = (beta - alpha) / (2.0 * gamma);
-          const double root = __builtin_sqrt(zeta * zeta + 1.0);
-          const double t = zeta >= 0.0 ? 1.0 / (zeta + root) : 1.0 / (zeta - root);
-          c = 1.0 / __builtin_sqrt(t * t + 1.0);
-          s = t * c;
-        }
-      }
-      __syncthreads();  // every group has read its two columns
-      if (rot)
-        for (int row = gl; row < M + N; row += kPairLanes) {
-          double* x = row < M ? &S.A[row * N] : &S.V[(row - M) * N];
-          const double xp = x[p], xq = x[q];
-          x[p] = c * xp - s * xq;
-          x[q] = s * xp + c * xq;
-        }
-      __syncthreads();
-    }
-  double s[N];
-  for (int j = 0; j < N; j++) {
-    double sum = 0.0;
-#pragma unroll
-    for (int r = 0; r < M; r++) sum += S.A[r * N + j] * S.A[r * N + j];
-    s[j] = __builtin_sqrt(sum);
-    ord[j] = j;
-  }
-  for (int i = 1; i < N; i++)
-    for (int j = i; j > 0 && s[ord[j - 1]] < s[ord[j]]; j--) {
-      const int tmp = ord[j];
-      ord[j] = ord[j - 1];
-      ord[j - 1] = tmp;
-    }
-  for (int k = 0; k < N; k++) d[k] = s[ord[k]];
-}
+// ---- the one SVD: svd_lds of jacobi_svd.h ------------------------------------------------------
 
 // x (N) from the SVD in S.A / S.V / d / ord: least squares, minimum norm when rank-deficient.
 template <int M, int N>
@@ -211,7 +145,7 @@ __device__ __forceinline__ void lstsq6(WaveLds& S, int lane, const double* l, co
   double d[N];
   int ord[N];
   put_A<6 * N>(S, l, lane);
-  svd_lds<6, N>(S, lane, d, ord);
+  svd_lds<6, N, kSweeps>(S, lane, d, ord);
   svd_backsolve<6, N>(S, d, ord, rho, x);
 }
 
@@ -288,7 +222,7 @@ __device__ __noinline__ void choose_control_points(Epnp& E, WaveLds& S, int lane
   double dc[3];
   int ord[3];
   put_A<9>(S, pw0tpw0, lane);
-  svd_lds<3, 3>(S, lane, dc, ord);
+  svd_lds<3, 3, kSweeps>(S, lane, dc, ord);
   for (int i = 1; i < 4; i++) {
     const double k = __builtin_sqrt(dc[i - 1] / n);
     for (int j = 0; j < 3; j++) E.cws[i][j] = E.cws[0][j] + k * S.V[j * 3 + ord[i - 1]];
@@ -301,7 +235,7 @@ __device__ __noinline__ void compute_cc_inv(Epnp& E, WaveLds& S, int lane) {
   for (int i = 0; i < 3; i++)
     for (int j = 1; j < 4; j++) cc[3 * i + j - 1] = E.cws[j][i] - E.cws[0][i];
   put_A<9>(S, cc, lane);
-  svd_lds<3, 3>(S, lane, d, ord);
+  svd_lds<3, 3, kSweeps>(S, lane, d, ord);
   for (int j = 0; j < 3; j++) {
     double e[3] = {0.0, 0.0, 0.0}, x[3];
     e[j] = 1.0;
@@ -351,7 +285,7 @@ __device__ __noinline__ void compute_mtm_eig(Epnp& E, WaveLds& S, int lane) {
   __syncthreads();
   double d[12];
   int ord[12];
-  svd_lds<12, 12>(S, lane, d, ord);
+  svd_lds<12, 12, kSweeps>(S, lane, d, ord);
   for (int i = 0; i < 4; i++)
     for (int c = 0; c < 12; c++) E.v4[i][c] = S.V[c * 12 + ord[11 - i]];
 }
@@ -562,7 +496,7 @@ __device__ __noinline__ double compute_R_and_t(Epnp& E, WaveLds& S, int lane, co
   double d[3];
   int ord[3];
   put_A<9>(S, abt, lane);
-  svd_lds<3, 3>(S, lane, d, ord);
+  svd_lds<3, 3, kSweeps>(S, lane, d, ord);
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++)
       R[3 * i + j] = (S.A[i * 3 + ord[0]] / d[0]) * S.V[j * 3 + ord[0]] +

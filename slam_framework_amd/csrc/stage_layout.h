@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/slamgpu_bow.h"
+#include "../../include/slamgpu_initializer.h"
 #include "../../include/slamgpu_loopmatch.h"
 #include "../../include/slamgpu_optimizer.h"
 #include "../../include/slamgpu_pnpsolver.h"
@@ -168,6 +169,22 @@ inline PnpRansacLayout layout_pnp_ransac(StageLayout& L, size_t n, size_t n_its)
           L.take<uint64_t>(n_its * SLAMGPU_PNP_MASK_WORDS(n)), L.take<slamgpu_pnp_hyp>(n_its),
           L.take<uint64_t>(n_its * SLAMGPU_PNP_MASK_WORDS(n)), L.take<int32_t>(n_its),
           L.take<int32_t>(1)};
+}
+
+// The monocular Initializer of one pair of frames: n1 and n2 keys, n_its iterations of 8 draws;
+// every row is sized by n1 and n_its, the mask rows are SLAMGPU_INIT_MASK_WORDS(n1) words each.
+struct InitRansacLayout {
+  size_t keys1, matches12, keys2, draws, job, hyp, bits, result, pairs, motion, good_bits, p3d;
+};
+inline InitRansacLayout layout_init_ransac(StageLayout& L, size_t n1, size_t n2, size_t n_its) {
+  const size_t words = SLAMGPU_INIT_MASK_WORDS(n1);
+  return {L.take<float>(2 * n1), L.take<int32_t>(n1), L.take<float>(2 * n2),
+          L.take<int32_t>(8 * n_its), L.take<slamgpu_init_job>(1),
+          L.take<slamgpu_init_hyp>(2 * n_its), L.take<uint64_t>(2 * n_its * words),
+          L.take<slamgpu_init_result>(1), L.take<int32_t>(2 * n1),
+          L.take<slamgpu_init_motion>(SLAMGPU_INIT_MAX_MOTIONS),
+          L.take<uint64_t>(SLAMGPU_INIT_MAX_MOTIONS * words),
+          L.take<float>(SLAMGPU_INIT_MAX_MOTIONS * 3 * n1)};
 }
 
 // A host FeatureVector (n_nodes > 0) must be well formed before its indices reach the device:

@@ -64,6 +64,22 @@ PNP_MAX_MATCHES = 4096
 PNP_RANSAC_MAX_ITS = 512
 assert PNP_MATCH_DTYPE.itemsize == 24 and PNP_JOB_DTYPE.itemsize == 24
 assert PNP_HYP_DTYPE.itemsize == 64
+# slamgpu_init_job / _hyp / _result / _motion (include/slamgpu_initializer.h): one pair of frames
+# of the monocular Initializer, one H or F hypothesis, the per-job selection, one motion hypothesis.
+INIT_JOB_DTYPE = np.dtype([("key1_begin", "<i4"), ("n1", "<i4"), ("key2_begin", "<i4"),
+                           ("n2", "<i4"), ("draw_begin", "<i4"), ("n_its", "<i4"),
+                           ("K", "<f4", (4,)), ("sigma", "<f4"), ("pad", "<i4")])
+INIT_HYP_DTYPE = np.dtype([("M", "<f4", (9,)), ("score", "<f4"), ("pad", "<i4", (2,))])
+INIT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("n", "<i4"), ("best", "<i4", (2,)),
+                              ("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"), ("model", "<i4"),
+                              ("n_motions", "<i4"), ("norm", "<f4", (8,)), ("pad", "<i4", (3,))])
+INIT_MOTION_DTYPE = np.dtype([("R", "<f4", (9,)), ("t", "<f4", (3,)), ("n_good", "<i4"),
+                              ("cos_parallax", "<f4"), ("pad", "<i4", (2,))])
+INIT_MAX_KEYS = 8192
+INIT_MAX_ITS = 512
+INIT_MAX_MOTIONS = 8
+assert INIT_JOB_DTYPE.itemsize == 48 and INIT_HYP_DTYPE.itemsize == 48
+assert INIT_RESULT_DTYPE.itemsize == 80 and INIT_MOTION_DTYPE.itemsize == 64
 # slamgpu_sim3_edge (include/slamgpu_optimizer.h): one EdgeSim3 of the essential graph.
 SIM3_EDGE_DTYPE = np.dtype([("i", "<i4"), ("j", "<i4"), ("pad", "<i4", (2,)), ("Sji", "<f8", (8,))])
 # slamgpu_pose_edge (include/slamgpu_optimizer.h): one PoseOptimization correspondence.
@@ -115,6 +131,8 @@ EXPORTS = [
     "slamgpu_sim3solver_last_error", "slamgpu_sim3_ransac", "slamgpu_sim3_ransac_device",
     # include/slamgpu_pnpsolver.h
     "slamgpu_pnpsolver_last_error", "slamgpu_pnp_ransac", "slamgpu_pnp_ransac_device",
+    # include/slamgpu_initializer.h
+    "slamgpu_initializer_last_error", "slamgpu_init_ransac", "slamgpu_init_ransac_device",
     # include/slamgpu_io.h
     "slamgpu_io_last_error", "slamgpu_kitti_load_images", "slamgpu_kitti_image_path",
     "slamgpu_png_info", "slamgpu_png_decode", "slamgpu_imread_png",
@@ -269,6 +287,13 @@ def lib():
                                              vp, C.POINTER(ip)]
             L.slamgpu_pnp_ransac_device.argtypes = [vp, vp, ip, fp, vp, ip, vp, ip, vp, ip, ip,
                                                     ip, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "slamgpu_init_ransac"):  # include/slamgpu_initializer.h (absent from older A/B builds)
+            L.slamgpu_initializer_last_error.argtypes = []
+            L.slamgpu_initializer_last_error.restype = C.c_char_p
+            L.slamgpu_init_ransac.argtypes = [vp, vp, ip, vp, ip, vp, fp, vp, ip, vp, vp, vp, vp,
+                                              vp, vp, vp]
+            L.slamgpu_init_ransac_device.argtypes = [vp, vp, ip, vp, ip, vp, ip, vp, ip, ip, ip,
+                                                     vp, vp, vp, vp, vp, vp, vp, vp]
         L.slamgpu_optimizer_last_error.argtypes = []
         L.slamgpu_optimizer_last_error.restype = C.c_char_p
         if hasattr(L, "slamgpu_coop_slots_in_use"):  # diagnostic (absent from older A/B builds)
@@ -1280,6 +1305,144 @@ class PnPsolver:
             self.SetRansacParameters(*self._params)
         T, _, vb, n = self.iterate(self.mRansacMaxIts)
         return T, vb, n
+
+
+def _init_check(rc):
+    if rc != 0:
+        raise SlamGpuError(f"slamgpu initializer error {rc}: "
+                           f"{lib().slamgpu_initializer_last_error().decode()}")
+
+
+def init_ransac_device(d_keys1, d_matches12, n_keys1_total, d_keys2, n_keys2_total, d_draws,
+                       n_draws_total, d_jobs, n_jobs, max_n1, max_its, d_hyp, d_bits, d_result,
+                       d_pairs, d_motion, d_good_bits, d_p3d, stream=None):
+    """slamgpu_init_ransac_device: the monocular Initializer of a batch of frame pairs in HBM
+    (keys float32 [n][2]; matches12 int32; jobs INIT_JOB_DTYPE; hyp [n_jobs][2][max_its]
+    INIT_HYP_DTYPE; bits [n_jobs][2][max_its][ceil(max_n1 / 64)] uint64; result [n_jobs]
+    INIT_RESULT_DTYPE; pairs [n_jobs][max_n1][2] int32; motion [n_jobs][8] INIT_MOTION_DTYPE;
+    good_bits [n_jobs][8][words] uint64; p3d [n_jobs][8][max_n1][3] float32)."""
+    _init_check(lib().slamgpu_init_ransac_device(
+        _ptr(d_keys1), _ptr(d_matches12), int(n_keys1_total), _ptr(d_keys2), int(n_keys2_total),
+        _ptr(d_draws), int(n_draws_total), _ptr(d_jobs), int(n_jobs), int(max_n1), int(max_its),
+        _ptr(d_hyp), _ptr(d_bits), _ptr(d_result), _ptr(d_pairs), _ptr(d_motion),
+        _ptr(d_good_bits), _ptr(d_p3d), C.c_void_p(stream) if stream else None))
+
+
+def init_ransac(keys1, keys2, matches12, K, sigma, draws, n_its):
+    """slamgpu_init_ransac (synchronous, one pair of frames): returns (hyp[2][n_its]
+    INIT_HYP_DTYPE, bits[2][n_its][ceil(n1 / 64)] uint64, result INIT_RESULT_DTYPE record,
+    pairs[N][2], motion[n_motions] INIT_MOTION_DTYPE, good_bits[n_motions][words],
+    p3d[n_motions][n1][3])."""
+    k1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+    k2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+    m = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+    K = np.ascontiguousarray(K, np.float32).reshape(-1)
+    d = np.ascontiguousarray(draws, np.int32).reshape(-1)
+    if len(K) != 4:
+        raise ValueError("K = (fx, fy, cx, cy)")
+    if len(m) != len(k1):
+        raise ValueError("one matches12 entry per key of frame 1")
+    if len(d) < 8 * int(n_its):
+        raise ValueError("eight draws per iteration are needed")
+    n1, rows = len(k1), max(int(n_its), 1)
+    words = max((n1 + 63) // 64, 1)
+    hyp = np.zeros((2, rows), INIT_HYP_DTYPE)
+    bits = np.zeros((2, rows, words), np.uint64)
+    result = np.zeros(1, INIT_RESULT_DTYPE)
+    pairs = np.zeros((max(n1, 1), 2), np.int32)
+    motion = np.zeros(INIT_MAX_MOTIONS, INIT_MOTION_DTYPE)
+    good = np.zeros((INIT_MAX_MOTIONS, words), np.uint64)
+    p3d = np.zeros((INIT_MAX_MOTIONS, max(n1, 1), 3), np.float32)
+    _init_check(lib().slamgpu_init_ransac(_ptr(k1), _ptr(m), n1, _ptr(k2), len(k2), _ptr(K),
+                                          float(sigma), _ptr(d), int(n_its), _ptr(hyp), _ptr(bits),
+                                          _ptr(result), _ptr(pairs), _ptr(motion), _ptr(good),
+                                          _ptr(p3d)))
+    r = result[0]
+    nm = int(r["n_motions"])
+    return hyp, bits, r, pairs[:int(r["n"])], motion[:nm], good[:nm], p3d[:nm, :n1]
+
+
+_seeded_once = False
+
+
+def seed_rand_once(seed):
+    """DUtils::Random::SeedRandOnce(int) (DUtils/Random.cpp:38-45): srand(seed) the first time
+    in the process."""
+    global _libc, _seeded_once
+    if not _seeded_once:
+        if _libc is None:
+            _libc = C.CDLL(None)
+        _libc.srand(int(seed))
+        _seeded_once = True
+
+
+class Initializer:
+    """The reference's Initializer (src/util/initializer.h): keys1 = the reference frame's
+    undistorted keypoint positions [n1][2], K = (fx, fy, cx, cy). Initialize draws the schedule
+    with random_int(min, max) as initializer.cpp:60-77 does (SeedRandOnce(0) first when the
+    generator is the default rand()), evaluates it in ONE synchronous device call and replays
+    :92-98 and the tails of ReconstructH / ReconstructF on the host."""
+
+    def __init__(self, keys1, K, sigma=1.0, iterations=200, random_int=None):
+        self.keys1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        self.K = np.ascontiguousarray(K, np.float32).reshape(-1)
+        self.sigma = float(sigma)
+        self.iterations = int(iterations)
+        self._default_rand = random_int is None
+        self.random_int = random_int or reference_random_int
+        self.device_calls = 0
+
+    def Initialize(self, keys2, vMatches12, minParallax=1.0, minTriangulated=50):
+        """Returns (ok, R21 3x3 f32, t21 f32[3], vP3D f32[n1][3], vbTriangulated bool[n1]); the
+        last four are None when ok is False."""
+        m = np.ascontiguousarray(vMatches12, np.int32).reshape(-1)
+        n1 = len(self.keys1)
+        N = int((m >= 0).sum())
+        if self._default_rand:
+            seed_rand_once(0)
+        draws = np.zeros((self.iterations, 8), np.int32)
+        for k in range(self.iterations):
+            for j in range(8):
+                draws[k, j] = self.random_int(0, N - 1 - j)
+        hyp, bits, r, pairs, motion, good, p3d = init_ransac(
+            self.keys1, keys2, m, self.K, self.sigma, draws, self.iterations)
+        self.device_calls += 1
+        self.result, self.hyp, self.motion = r, hyp, motion
+        fail = (False, None, None, None, None)
+        model, nm = int(r["model"]), len(motion)
+        b = int(r["best"][model])
+        if b < 0 or nm == 0:  # FindFundamental's empty mask, or the early return of :601
+            return fail
+        Nin = int(np.unpackbits(bits[model, b].view(np.uint8), bitorder="little")[:N].sum())
+        ng = motion["n_good"].astype(np.int64)
+        cosv = motion["cos_parallax"].astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            parallax = np.where(ng > 0, np.float32(np.arccos(cosv) * 180 / np.pi),
+                                np.float32(0)).astype(np.float32)
+        minParallax = np.float32(minParallax)
+        if model == 1:  # ReconstructF :495-565
+            maxGood = int(ng.max())
+            nMinGood = max(int(0.9 * Nin), minTriangulated)
+            nsimilar = int((ng > 0.7 * maxGood).sum())
+            if maxGood < nMinGood or nsimilar > 1:
+                return fail
+            i = int(np.argmax(ng == maxGood))
+            if not parallax[i] > minParallax:
+                return fail
+        else:  # ReconstructH :693-735
+            bestGood = secondBestGood = 0
+            i, bestParallax = -1, np.float32(-1)
+            for j in range(nm):
+                if ng[j] > bestGood:
+                    secondBestGood, bestGood, i, bestParallax = bestGood, int(ng[j]), j, parallax[j]
+                elif ng[j] > secondBestGood:
+                    secondBestGood = int(ng[j])
+            if not (secondBestGood < 0.75 * bestGood and bestParallax >= minParallax
+                    and bestGood > minTriangulated and bestGood > 0.9 * Nin):
+                return fail
+        vb = np.unpackbits(good[i].view(np.uint8), bitorder="little")[:n1].astype(bool)
+        return (True, motion["R"][i].reshape(3, 3).copy(), motion["t"][i].copy(), p3d[i].copy(),
+                vb)
 
 
 def pose_optimization_device(cam, inv_sigma2, d_edges, d_edge_start, n_frames, d_Tcw, d_outlier,
