@@ -73,7 +73,8 @@ void launch_extract(const ImageBatch& b, const OrbGeomDev& g, int n_images, hipS
 // key capacities within these.
 hipError_t octree_lds_limits(int device, int* img_bytes, int* lvl_bytes);
 // The geometry was laid out with the kernels' own build constants (ring strip, FAST key group):
-// false when orb_geometry.cpp and orb_kernels.hip were built with different -D flags.
+// false when orb_geometry.cpp and orb_pyramid.hip / orb_fast.hip were built with different -D
+// flags.
 bool extract_build_matches(const OrbGeom& g);
 
 }  // namespace slamgpu

@@ -267,8 +267,8 @@ int slamgpu_create(int device, const slamgpu_orb_params* p, int cols, int rows, 
   if (!extract_build_matches(c->geom)) {
     delete c;
     return t_create_err.fail(SLAMGPU_EINVAL,
-                       "slamgpu_create: orb_geometry.cpp and orb_kernels.hip were built with "
-                       "different PYR_RING_STRIP / FAST_CELLS_PER_WAVE");
+                       "slamgpu_create: orb_geometry.cpp and orb_pyramid.hip / orb_fast.hip were "
+                       "built with different PYR_RING_STRIP / FAST_CELLS_PER_WAVE");
   }
   compute_tables(c->params, &c->tables);
   if (c->geom.kp_cap > 4096) {  // matcher keys carry a 12-bit keypoint index

@@ -12,7 +12,7 @@ The expectations restate the reference in NumPy float32, statement by statement:
 * OpenCV 3.3.1 resize (INTER_LINEAR): source rows sy = floor((dy + 0.5) * scale_y - 0.5), sy + 1,
   clamped to the source.
 Nothing here is derived from orb_geometry.cpp; the layout invariants are what the kernels that
-consume the geometry need (orb_kernels.hip), stated where they are asserted."""
+consume the geometry need (csrc/orb_*.hip), stated where they are asserted."""
 import numpy as np
 import pytest
 

@@ -1,7 +1,7 @@
 """Minimal unifdef: resolve the #if/#ifdef/#ifndef/#else/#endif blocks that test only the given
 macros (their values fixed), drop their #define / #ifndef-default lines, keep every other
 directive. Used to take rejected build variants out of a kernel source.
-  python tools/unifdef.py FILE OD_PAIRS=0 OD_MFMA=0 OCT_PROFILE=undef ...
+  python tools/unifdef.py FILE OD_PAIRS=0 OD_MFMA=0 FAST_PRE2=undef ...
 """
 import re
 import sys
