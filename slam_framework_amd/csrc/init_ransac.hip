@@ -26,7 +26,9 @@
 // and the two are compared bit for bit. Float division and square root are written through double
 // (exact: 53 >= 2 * 24 + 2). The library is built -ffp-contract=off; nothing here turns
 // contraction back on. The 16 x 9 and 8 x 9 SVDs are svd_lds of jacobi_svd.h, shared with
-// pnp_ransac.hip, with this solver's own sweep count.
+// pnp_ransac.hip, the 3 x 3 and 4 x 4 ones its one-lane svd_lane, with this solver's own sweep
+// count. The draw checks, the swap-and-pop, the mask word, the compaction and the best of a wave
+// are ransac_device.h's, as in the other solvers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -36,6 +38,7 @@
 #include "device_math.h"
 #include "host_stage.h"
 #include "jacobi_svd.h"
+#include "ransac_device.h"
 #include "stage_layout.h"
 
 namespace slamgpu {
@@ -55,80 +58,10 @@ struct SvdLds {
   int idx[8];
 };
 
-// The same routine on one lane for the square 3 x 3 and 4 x 4 matrices: A (float, row-major) ->
-// d[N], vt[N][N] rows = columns of V, ut[N][N] rows = columns of A V over their norms.
-template <int N>
-__device__ __forceinline__ void svd_lane(const float* A_in, double* d, double* vt, double* ut) {
-  double A[N * N], V[N * N], s[N];
-  int ord[N];
-#pragma unroll
-  for (int i = 0; i < N * N; i++) {
-    A[i] = (double)A_in[i];
-    V[i] = (i / N == i % N) ? 1.0 : 0.0;
-  }
-  constexpr int NP = N + (N & 1);
-#pragma unroll 1
-  for (int sw = 0; sw < kSweeps; sw++)
-#pragma unroll
-    for (int round = 0; round < NP - 1; round++)
-#pragma unroll
-      for (int i = 0; i < NP / 2; i++) {
-        const int a = i == 0 ? NP - 1 : (round + i) % (NP - 1);
-        const int b = i == 0 ? round : (round - i + NP - 1) % (NP - 1);
-        if (a >= N || b >= N) continue;  // the bye
-        const int p = a < b ? a : b, q = a < b ? b : a;
-        double alpha = 0.0, beta = 0.0, gamma = 0.0;
-#pragma unroll
-        for (int r = 0; r < N; r++) {
-          const double ap = A[r * N + p], aq = A[r * N + q];
-          alpha += ap * ap;
-          beta += aq * aq;
-          gamma += ap * aq;
-        }
-        if (!(__builtin_fabs(gamma) > 1e-15 * __builtin_sqrt(alpha * beta))) continue;
-        const double zeta = (beta - alpha) / (2.0 * gamma);
-        const double root = __builtin_sqrt(zeta * zeta + 1.0);
-        const double t = zeta >= 0.0 ? 1.0 / (zeta + root) : 1.0 / (zeta - root);
-        const double c = 1.0 / __builtin_sqrt(t * t + 1.0);
-        const double sn = t * c;
-#pragma unroll
-        for (int r = 0; r < N; r++) {
-          const double ap = A[r * N + p], aq = A[r * N + q];
-          A[r * N + p] = c * ap - sn * aq;
-          A[r * N + q] = sn * ap + c * aq;
-          const double vp = V[r * N + p], vq = V[r * N + q];
-          V[r * N + p] = c * vp - sn * vq;
-          V[r * N + q] = sn * vp + c * vq;
-        }
-      }
-#pragma unroll
-  for (int j = 0; j < N; j++) {
-    double sum = 0.0;
-#pragma unroll
-    for (int r = 0; r < N; r++) sum += A[r * N + j] * A[r * N + j];
-    s[j] = __builtin_sqrt(sum);
-    ord[j] = j;
-  }
-  for (int i = 1; i < N; i++)
-    for (int j = i; j > 0 && s[ord[j - 1]] < s[ord[j]]; j--) {
-      const int tmp = ord[j];
-      ord[j] = ord[j - 1];
-      ord[j - 1] = tmp;
-    }
-  for (int k = 0; k < N; k++) {
-    const int j = ord[k];
-    d[k] = s[j];
-    for (int r = 0; r < N; r++) {
-      vt[k * N + r] = V[r * N + j];
-      ut[k * N + r] = A[r * N + j] / s[j];
-    }
-  }
-}
-
 // cv::SVD::compute of a 3 x 3 CV_32F Mat: w, u, vt as float.
 __device__ __noinline__ void svd3(const float* A, float* w, float* u, float* vt) {
   double d[3], vtd[9], utd[9];
-  svd_lane<3>(A, d, vtd, utd);
+  svd_lane<3, kSweeps>(A, d, vtd, utd);
   for (int k = 0; k < 3; k++) {
     w[k] = (float)d[k];
     for (int r = 0; r < 3; r++) {
@@ -249,12 +182,7 @@ __global__ __launch_bounds__(64) void init_prep_kernel(
     bad |= m < -1 || m >= J.n2;
     n += __popcll(__ballot(m >= 0));
   }
-  if (n >= 8)
-    for (int i = lane; i < 8 * J.n_its; i += 64) {
-      const int r = draws[J.draw_begin + i];
-      bad |= r < 0 || r > n - 1 - i % 8;
-    }
-  if (n < 8 || __ballot(bad) != 0) {
+  if (n < 8 || __ballot(bad) != 0 || !draws_ok<8>(draws + J.draw_begin, J.n_its, n, lane)) {
     if (lane == 0) res->status = -1;
     return;
   }
@@ -264,13 +192,11 @@ __global__ __launch_bounds__(64) void init_prep_kernel(
   for (int base = 0; base < J.n1; base += 64) {
     const int i = base + lane;
     const int m = i < J.n1 ? m12[i] : -1;
-    const uint64_t mask = __ballot(m >= 0);
+    const int at = compact_slot(__ballot(m >= 0), c);
     if (m >= 0) {
-      const int at = c + __popcll(mask & (((uint64_t)1 << lane) - 1));
       jp[2 * at] = i;
       jp[2 * at + 1] = m;
     }
-    c += __popcll(mask);
   }
   // Normalize: lane = 2 * frame + coordinate
   if (lane < 4) {
@@ -356,26 +282,7 @@ __global__ __launch_bounds__(64) void init_hyp_kernel(
   const float* k1 = keys1 + 2 * (size_t)J.key1_begin;
   const float* k2 = keys2 + 2 * (size_t)J.key2_begin;
   const int32_t* jp = pairs + (size_t)job * max_n1 * 2;
-  // the sample: idx = avail[randi], avail[randi] = avail.back(), pop_back -- eight times. avail is
-  // the identity but for the (position, value) pairs written so far; later writes win.
-  if (lane == 0) {
-    const int32_t* jd = draws + J.draw_begin + 8 * k;
-    int pos[8], val[8], size = n;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int r = jd[i];
-      int at_r = r, at_back = size - 1;
-#pragma unroll
-      for (int j = 0; j < i; j++) {
-        if (pos[j] == r) at_r = val[j];
-        if (pos[j] == size - 1) at_back = val[j];
-      }
-      S.idx[i] = at_r;
-      pos[i] = r;
-      val[i] = at_back;
-      size--;
-    }
-  }
+  if (lane == 0) resolve_sample<8>(draws + J.draw_begin + 8 * k, n, S.idx);  // :64-76
   __syncthreads();
   if (lane < 8) {  // the rows of A (:215-242, :258-274) from the normalised points (:777-793)
     const int a = jp[2 * S.idx[lane]], b = jp[2 * S.idx[lane] + 1];
@@ -439,8 +346,7 @@ __global__ __launch_bounds__(64) void init_hyp_kernel(
       else
         terms_f(M, P, invSigmaSquare, t1, t2, in);
     }
-    const uint64_t mask = __ballot(in);
-    if (lane == 0) hb[w] = mask;
+    store_mask_word(in, hb + w, lane);
     // score += th - chi in match order, image 1 then image 2. A term that the reference skips is
     // +0 here: the score is never -0, so adding it changes nothing.
     if (w * 64 < n) {
@@ -469,7 +375,7 @@ __device__ __forceinline__ void decompose_e(const float* E, float* R1, float* R2
   float Et[9], u[9], vt[9], tmp[9];
   double d[3], vtd[9], utd[9], v[3][3];
   transpose3(E, Et);
-  svd_lane<3>(Et, d, vtd, utd);
+  svd_lane<3, kSweeps>(Et, d, vtd, utd);
   for (int k = 0; k < 2; k++)
     for (int r = 0; r < 3; r++) v[k][r] = utd[3 * k + r];
   v[2][0] = v[0][1] * v[1][2] - v[0][2] * v[1][1];
@@ -583,15 +489,7 @@ __global__ __launch_bounds__(64) void init_select_kernel(
         bi = k;
       }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const float os = __shfl_xor(bs, off, 64);
-      const int oi = __shfl_xor(bi, off, 64);
-      if (os > bs || (os == bs && oi >= 0 && (bi < 0 || oi < bi))) {
-        bs = os;
-        bi = oi;
-      }
-    }
+    wave_first_best(bs, bi);
     S[model] = bs;
     best[model] = bi;
   }
@@ -640,7 +538,7 @@ __device__ __noinline__ void triangulate(const float* kp1, const float* kp2, con
     A[12 + c] = kp2[1] * P2[8 + c] - P2[4 + c];
   }
   double d[4], vt[16], ut[16];
-  svd_lane<4>(A, d, vt, ut);
+  svd_lane<4, kSweeps>(A, d, vt, ut);
   const float x[4] = {(float)vt[12], (float)vt[13], (float)vt[14], (float)vt[15]};
   const float s = (float)(1.0 / (double)x[3]);
 #pragma unroll
@@ -843,10 +741,7 @@ int slamgpu_init_ransac(const float* keys1, const int32_t* matches12, int n1, co
     n += matches12[i] >= 0;
   }
   if (n < 8) return t_init_err.fail(SLAMGPU_EINVAL, "%d matches < 8", n);
-  for (int i = 0; i < 8 * n_its; i++)
-    if (draws[i] < 0 || draws[i] > n - 1 - i % 8)
-      return t_init_err.fail(SLAMGPU_EINVAL, "iteration %d: draw %d = %d outside [0, %d]", i / 8,
-                             i % 8, draws[i], n - 1 - i % 8);
+  if (int r = check_draws<8>(t_init_err, draws, n_its, n)) return r;
   const size_t words = SLAMGPU_INIT_MASK_WORDS(n1);
   StageLease S(t_init_err);
   StageLayout L;

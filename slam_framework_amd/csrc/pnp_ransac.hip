@@ -30,7 +30,8 @@
 //
 // Arithmetic: DESIGN.md "RANSAC EPnP solver"; tests/pnpsolver_ref.c restates it on the CPU and
 // the two are compared bit for bit. The library is built -ffp-contract=off; nothing here turns
-// contraction back on.
+// contraction back on. The SVD is svd_lds of jacobi_svd.h; the draw checks, the swap-and-pop, the
+// mask word, the compaction and the best of a wave are ransac_device.h's, as in the other solvers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -40,6 +41,7 @@
 #include "device_math.h"
 #include "host_stage.h"
 #include "jacobi_svd.h"
+#include "ransac_device.h"
 #include "stage_layout.h"
 
 namespace slamgpu {
@@ -73,29 +75,21 @@ __device__ __forceinline__ bool job_ranges_ok(const slamgpu_pnp_ransac_job& J, i
   return true;
 }
 
-// Draw i of the job (i % 4 = its place in the sample) lies in [0, n - 1 - i % 4]. Only called
-// for a job whose ranges are inside the arrays.
-__device__ __forceinline__ bool draw_ok(const int32_t* draws, int i, int n) {
-  const int r = draws[i];
-  return r >= 0 && r <= n - 1 - i % 4;
-}
-
 // One wave validates the whole job.
 __device__ __forceinline__ bool job_ok(const slamgpu_pnp_ransac_job& J, const int32_t* draws,
                                        int n_matches_total, int n_draws_total, int max_n,
                                        int max_its, int lane) {
-  if (!job_ranges_ok(J, n_matches_total, n_draws_total, max_n, max_its)) return false;
-  int bad = 0;
-  for (int i = lane; i < 4 * J.n_its; i += 64) bad |= !draw_ok(draws + J.draw_begin, i, J.n);
-  return __ballot(bad) == 0;
+  return job_ranges_ok(J, n_matches_total, n_draws_total, max_n, max_its) &&
+         draws_ok<4>(draws + J.draw_begin, J.n_its, J.n, lane);
 }
 
 // ---- sums over correspondences ---------------------------------------------------------------
 
-// part[e] of every lane -> tot[e] of every lane, the 64 partials added in lane order.
+// part[e] of every lane -> tot[e] of every lane, the 64 partials added in lane order (not the
+// butterfly wave_sum of device_math.h, whose order of additions is another).
 template <int K>
-__device__ __forceinline__ void wave_sum(WaveLds& S, const double (&part)[K], double (&tot)[K],
-                                         int lane) {
+__device__ __forceinline__ void ordered_wave_sum(WaveLds& S, const double (&part)[K],
+                                                 double (&tot)[K], int lane) {
 #pragma unroll
   for (int e = 0; e < K; e++) S.part[e * 64 + lane] = part[e];
   __syncthreads();
@@ -205,7 +199,7 @@ __device__ __noinline__ void choose_control_points(Epnp& E, WaveLds& S, int lane
 #pragma unroll
     for (int j = 0; j < 3; j++) p3[j] += P.w[j];
   }
-  wave_sum<3>(S, p3, t3, lane);
+  ordered_wave_sum<3>(S, p3, t3, lane);
 #pragma unroll
   for (int j = 0; j < 3; j++) E.cws[0][j] = t3[j] / n;
   double p6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, t6[6];
@@ -217,7 +211,7 @@ __device__ __noinline__ void choose_control_points(Epnp& E, WaveLds& S, int lane
 #pragma unroll
       for (int b = a; b < 3; b++, e++) p6[e] += (P.w[a] - E.cws[0][a]) * (P.w[b] - E.cws[0][b]);
   }
-  wave_sum<6>(S, p6, t6, lane);
+  ordered_wave_sum<6>(S, p6, t6, lane);
   const double pw0tpw0[9] = {t6[0], t6[1], t6[2], t6[1], t6[3], t6[4], t6[2], t6[4], t6[5]};
   double dc[3];
   int ord[3];
@@ -271,7 +265,7 @@ __device__ __noinline__ void compute_mtm_eig(Epnp& E, WaveLds& S, int lane) {
         part[e] += M2[a] * M2[b];
       }
   }
-  wave_sum<kMtmSums>(S, part, tot, lane);
+  ordered_wave_sum<kMtmSums>(S, part, tot, lane);
   // S.tot still holds the 78 sums: entry (a, b), a <= b, is at 12 a - a (a - 1) / 2 + b - a
   for (int t = lane; t < 144; t += 64) {
     int a = t / 12, b = t % 12;
@@ -475,7 +469,7 @@ __device__ __noinline__ double compute_R_and_t(Epnp& E, WaveLds& S, int lane, co
       p6[3 + j] += P.w[j];
     }
   }
-  wave_sum<6>(S, p6, t6, lane);
+  ordered_wave_sum<6>(S, p6, t6, lane);
   double pc0[3], pw0[3];
 #pragma unroll
   for (int j = 0; j < 3; j++) {
@@ -492,7 +486,7 @@ __device__ __noinline__ double compute_R_and_t(Epnp& E, WaveLds& S, int lane, co
 #pragma unroll
       for (int c = 0; c < 3; c++) p9[3 * j + c] += (pc[j] - pc0[j]) * (P.w[c] - pw0[c]);
   }
-  wave_sum<9>(S, p9, abt, lane);
+  ordered_wave_sum<9>(S, p9, abt, lane);
   double d[3];
   int ord[3];
   put_A<9>(S, abt, lane);
@@ -522,7 +516,7 @@ __device__ __noinline__ double compute_R_and_t(Epnp& E, WaveLds& S, int lane, co
     const double ve = E.vc + E.fv * Yc * inv_Zc;
     p1[0] += __builtin_sqrt((P.u - ue) * (P.u - ue) + (P.v - ve) * (P.v - ve));
   }
-  wave_sum<1>(S, p1, t1, lane);
+  ordered_wave_sum<1>(S, p1, t1, lane);
   return t1[0] / n;
 }
 
@@ -580,9 +574,7 @@ __device__ __forceinline__ int check_inliers(const slamgpu_pnp_match* m, int n, 
       const int o = c.octave;
       if (o >= 0 && o < P.nlevels) in = error2 < P.thr[o];
     }
-    const uint64_t mask = __ballot(in);
-    if (lane == 0) bits[w] = mask;
-    cnt += __popcll(mask);
+    cnt += store_mask_word(in, bits + w, lane);
   }
   return cnt;
 }
@@ -612,26 +604,7 @@ __global__ __launch_bounds__(64) void pnp_hyp_kernel(
   if (k >= J.n_its) return;
   const int n = J.n;
   const slamgpu_pnp_match* m = matches + J.match_begin;
-  // the sample: idx = avail[randi], avail[randi] = avail.back(), pop_back -- four times. avail is
-  // the identity but for the (position, value) pairs written so far; later writes win.
-  if (lane == 0) {
-    const int32_t* jd = draws + J.draw_begin + 4 * k;
-    int pos[4], val[4], size = n;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int r = jd[i];
-      int at_r = r, at_back = size - 1;
-#pragma unroll
-      for (int j = 0; j < i; j++) {
-        if (pos[j] == r) at_r = val[j];
-        if (pos[j] == size - 1) at_back = val[j];
-      }
-      S.sel[i] = at_r;
-      pos[i] = r;
-      val[i] = at_back;
-      size--;
-    }
-  }
+  if (lane == 0) resolve_sample<4>(draws + J.draw_begin + 4 * k, n, S.sel);  // :144-154
   __syncthreads();
   double R[9], t[3];
   compute_pose(m, 4, P, S, lane, R, t);
@@ -665,29 +638,14 @@ __global__ __launch_bounds__(64) void pnp_refine_kernel(
       bi = j;
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const int oc = __shfl_xor(bc, off, 64), oi = __shfl_xor(bi, off, 64);
-    if (oc > bc || (oc == bc && oi >= 0 && (bi < 0 || oi < bi))) {
-      bc = oc;
-      bi = oi;
-    }
-  }
+  wave_first_best(bc, bi);
   const size_t row = (size_t)job * max_its + k;
   if (lane == 0) jh[k].best = bi;
   uint64_t* rb = refined_bits + row * words;
   if (bi != k) {
     for (int w = lane; w < words; w += 64) rb[w] = 0;
-    if (lane == 0) {
-      slamgpu_pnp_hyp h;
-#pragma unroll
-      for (int i = 0; i < 9; i++) h.Rcw[i] = 0.0f;
-#pragma unroll
-      for (int i = 0; i < 3; i++) h.tcw[i] = 0.0f;
-      h.n_inliers = h.best = -1;
-      h.pad[0] = h.pad[1] = 0;
-      refined[row] = h;
-    }
+    const double zero[9] = {};
+    if (lane == 0) refined[row] = make_hyp(zero, zero, -1, -1);
     return;
   }
   // Refine (:213-258): the inliers of the best, in ascending order
@@ -695,8 +653,8 @@ __global__ __launch_bounds__(64) void pnp_refine_kernel(
   int ns = 0;
   for (int w = 0; w < (n + 63) >> 6; w++) {
     const uint64_t mask = kb[w];
-    if (mask >> lane & 1) S.sel[ns + __popcll(mask & (((uint64_t)1 << lane) - 1))] = w * 64 + lane;
-    ns += __popcll(mask);
+    const int slot = compact_slot(mask, ns);
+    if (mask >> lane & 1) S.sel[slot] = w * 64 + lane;
   }
   __syncthreads();
   double R[9], t[3];
@@ -727,9 +685,8 @@ __global__ __launch_bounds__(64) void pnp_event_kernel(
       const int b = jh[k].best;  // >= 0: iteration k itself reached min_inliers
       ev = b >= 0 && b <= k && jr[b].n_inliers > J.min_inliers;
     }
-    const uint64_t mask = __ballot(ev);
-    if (ev) je[ne + __popcll(mask & (((uint64_t)1 << lane) - 1))] = k;
-    ne += __popcll(mask);
+    const int slot = compact_slot(__ballot(ev), ne);
+    if (ev) je[slot] = k;
   }
   if (lane == 0) n_events[job] = ne;
 }
@@ -809,10 +766,7 @@ int slamgpu_pnp_ransac(const float K[4], const float* sigma2, int nlevels, float
     return t_pnp_err.fail(SLAMGPU_EINVAL, "n_its %d outside [1, SLAMGPU_PNP_RANSAC_MAX_ITS (%d)]",
                           n_its, SLAMGPU_PNP_RANSAC_MAX_ITS);
   if (min_inliers < 4) return t_pnp_err.fail(SLAMGPU_EINVAL, "min_inliers %d < 4", min_inliers);
-  for (int i = 0; i < 4 * n_its; i++)
-    if (draws[i] < 0 || draws[i] > n - 1 - i % 4)
-      return t_pnp_err.fail(SLAMGPU_EINVAL, "iteration %d: draw %d = %d outside [0, %d]", i / 4,
-                            i % 4, draws[i], n - 1 - i % 4);
+  if (int r = check_draws<4>(t_pnp_err, draws, n_its, n)) return r;
   const size_t words = SLAMGPU_PNP_MASK_WORDS(n);
   StageLease S(t_pnp_err);
   StageLayout L;

@@ -4,7 +4,7 @@
 //
 //   sim3_hyp_kernel    grid (ceil(max_its / 4), jobs), 4 waves per workgroup, ONE WAVE PER
 //                      HYPOTHESIS. The wave resolves its three draws to correspondence indices
-//                      (the swap-and-pop of :173-179 in closed form), solves Horn once -- every
+//                      (the swap-and-pop of :173-179, on every lane), solves Horn once -- every
 //                      lane holds the same transform, the FP64 Jacobi costs a wave the same
 //                      whether one lane or 64 run it -- and strides over the correspondences 64 at
 //                      a time: one lane per correspondence, the ballot of err1 < max1 && err2 <
@@ -20,7 +20,9 @@
 //
 // Arithmetic: DESIGN.md "RANSAC Sim3 solver"; tests/sim3solver_ref.c restates it on the CPU and
 // the two are compared bit for bit. The library is built -ffp-contract=off; nothing here turns
-// contraction back on (the one fma is the reference's own, u = fx * x + cx).
+// contraction back on (the one fma is the reference's own, u = fx * x + cx). The draw checks, the
+// swap-and-pop, the mask word and the compaction are ransac_device.h's, as in the other solvers;
+// the angle of the two-sided Jacobi is jacobi_angle of jacobi_svd.h, as in their one-sided one.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -29,6 +31,8 @@
 #include "../../include/slamgpu_sim3solver.h"
 #include "device_math.h"
 #include "host_stage.h"
+#include "jacobi_svd.h"
+#include "ransac_device.h"
 #include "stage_layout.h"
 
 namespace slamgpu {
@@ -54,13 +58,6 @@ __device__ __forceinline__ bool job_ranges_ok(const slamgpu_sim3_ransac_job& J,
   return true;
 }
 
-// Draw i of the job (i % 3 = its place in the sample) lies in [0, n - 1 - i % 3]. Only called
-// for a job whose ranges are inside the arrays.
-__device__ __forceinline__ bool draw_ok(const int32_t* draws, int i, int n) {
-  const int r = draws[i];
-  return r >= 0 && r <= n - 1 - i % 3;
-}
-
 __device__ __forceinline__ float dot3(float a0, float a1, float a2, float b0, float b1, float b2) {
   return a0 * b0 + a1 * b1 + a2 * b2;
 }
@@ -70,11 +67,8 @@ template <int P, int Q>
 __device__ __forceinline__ void jacobi_rotate(double (&A)[4][4], double (&V)[4][4]) {
   const double apq = A[P][Q];
   if (apq == 0.0) return;
-  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-  const double root = __builtin_sqrt(theta * theta + 1.0);
-  const double t = theta >= 0.0 ? 1.0 / (theta + root) : 1.0 / (theta - root);
-  const double c = 1.0 / __builtin_sqrt(t * t + 1.0);
-  const double s = t * c;
+  double t, c, s;
+  jacobi_angle((A[Q][Q] - A[P][P]) / (2.0 * apq), t, c, s);
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     if (k == P || k == Q) continue;
@@ -232,18 +226,15 @@ __global__ __launch_bounds__(64 * kHypWaves) void sim3_hyp_kernel(
   if (!job_ranges_ok(J, n_matches_total, n_draws_total, max_n, max_its)) return;
   const int32_t* jd = draws + J.draw_begin;
   int bad = 0;
-  for (int i = threadIdx.x; i < 3 * J.n_its; i += 64 * kHypWaves) bad |= !draw_ok(jd, i, J.n);
+  for (int i = threadIdx.x; i < 3 * J.n_its; i += 64 * kHypWaves)
+    bad |= !draw_in_range<3>(jd[i], i, J.n);
   if (__syncthreads_or(bad)) return;
   const int k = blockIdx.x * kHypWaves + wave_id();
   if (k >= J.n_its) return;
   const int n = J.n, lane = lane_id();
   const slamgpu_sim3_match* m = matches + J.match_begin;
-  // the sample: avail[randi] of :173, avail[randi] = avail.back(), pop_back -- for three draws
-  const int r0 = jd[3 * k], r1 = jd[3 * k + 1], r2 = jd[3 * k + 2];
-  const int i0 = r0;
-  const int i1 = r1 == r0 ? n - 1 : r1;
-  const int i2 = r2 == r1 ? (r0 == n - 2 ? n - 1 : n - 2) : (r2 == r0 ? n - 1 : r2);
-  const int idx[3] = {i0, i1, i2};
+  int idx[3];  // the sample (:173-179), the same on every lane
+  resolve_sample<3>(jd + 3 * k, n, idx);
   float P1[9], P2[9];
 #pragma unroll
   for (int i = 0; i < 3; i++)
@@ -278,9 +269,7 @@ __global__ __launch_bounds__(64 * kHypWaves) void sim3_hyp_kernel(
       if (o1 >= 0 && o1 < P.nlevels && o2 >= 0 && o2 < P.nlevels)
         in = err1 < P.thr1[o1] && err2 < P.thr2[o2];
     }
-    const uint64_t mask = __ballot(in);
-    if (lane == 0) bits[w] = mask;
-    cnt += __popcll(mask);
+    cnt += store_mask_word(in, bits + w, lane);
   }
   if (lane == 0) {
     slamgpu_sim3_hyp h;
@@ -302,13 +291,8 @@ __global__ __launch_bounds__(64) void sim3_event_kernel(
     int32_t* __restrict__ n_events) {
   const int job = blockIdx.x, lane = lane_id();
   const slamgpu_sim3_ransac_job J = jobs[job];
-  bool ok = job_ranges_ok(J, n_matches_total, n_draws_total, max_n, max_its);
-  if (ok) {
-    int bad = 0;
-    for (int i = lane; i < 3 * J.n_its; i += 64) bad |= !draw_ok(draws + J.draw_begin, i, J.n);
-    ok = __ballot(bad) == 0;
-  }
-  if (!ok) {
+  if (!job_ranges_ok(J, n_matches_total, n_draws_total, max_n, max_its) ||
+      !draws_ok<3>(draws + J.draw_begin, J.n_its, J.n, lane)) {
     if (lane == 0) n_events[job] = -1;
     return;
   }
@@ -327,9 +311,8 @@ __global__ __launch_bounds__(64) void sim3_event_kernel(
     const int prev = __shfl_up(inc, 1, 64);
     const int excl = lane == 0 ? carry : (prev > carry ? prev : carry);
     const bool ev = k < J.n_its && v >= excl && v > J.min_inliers;
-    const uint64_t mask = __ballot(ev);
-    if (ev) je[ne + __popcll(mask & (((uint64_t)1 << lane) - 1))] = k;
-    ne += __popcll(mask);
+    const int slot = compact_slot(__ballot(ev), ne);
+    if (ev) je[slot] = k;
     const int last = __shfl(inc, 63, 64);
     carry = last > carry ? last : carry;
   }
@@ -414,10 +397,7 @@ int slamgpu_sim3_ransac(const float K1[4], const float K2[4], const float* sigma
   if (n_its < 1 || n_its > SLAMGPU_SIM3_RANSAC_MAX_ITS)
     return t_s3_err.fail(SLAMGPU_EINVAL, "n_its %d outside [1, SLAMGPU_SIM3_RANSAC_MAX_ITS (%d)]",
                          n_its, SLAMGPU_SIM3_RANSAC_MAX_ITS);
-  for (int i = 0; i < 3 * n_its; i++)
-    if (draws[i] < 0 || draws[i] > n - 1 - i % 3)
-      return t_s3_err.fail(SLAMGPU_EINVAL, "iteration %d: draw %d = %d outside [0, %d]", i / 3,
-                           i % 3, draws[i], n - 1 - i % 3);
+  if (int r = check_draws<3>(t_s3_err, draws, n_its, n)) return r;
   const size_t words = SLAMGPU_SIM3_MASK_WORDS(n);
   StageLease S(t_s3_err);
   StageLayout L;

@@ -79,6 +79,23 @@ def test_single_job_bit_exact(G, n, n_its):
     assert_job_equal(run_single(G, s, d, n_its), want, s.n1, n_its)
 
 
+def test_best_tie_goes_to_the_first_iteration(G):
+    """130 iterations: one hypothesis 70 times, then a better one 60 times, so iterations 70 .. 129
+    tie exactly in both models. In the selecting wave lane 6 holds iteration 70 and lane 0 only
+    iteration 128 as candidates: a tie decided by lane instead of by index would answer 128."""
+    s = S.make("planar", n=64, noise=0.5, extra1=40, extra2=25)
+    d0 = S.draws(64, 130, seed=71)
+    d = np.ascontiguousarray(np.concatenate([np.repeat(d0[3:4], 70, 0), np.repeat(d0[5:6], 60, 0)]))
+    want = R.ransac(s.keys1, s.keys2, s.matches12, s.K, s.sigma, d, 130)
+    w = want.result[0]
+    assert w["best"].tolist() == [70, 70] and (w["model"], w["n_motions"]) == (0, 8)
+    score = np.ascontiguousarray(want.hyp["score"][:, :130]).view(np.uint32)
+    for model in (0, 1):
+        assert (score[model, 70:] == score[model, 70]).all()
+        assert (want.hyp["score"][model, :70] < want.hyp["score"][model, 70]).all()
+    assert_job_equal(run_single(G, s, d, 130), want, s.n1, 130)
+
+
 def test_cap(G):
     """N = n1 = SLAMGPU_INIT_MAX_KEYS."""
     s, d, want = case("general", G.INIT_MAX_KEYS, 0.0, 16, 0, 0)

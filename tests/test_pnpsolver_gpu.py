@@ -90,6 +90,23 @@ def test_single_job_bit_exact(G, n):
             assert not (np.asarray(b, np.uint64)[:, -1] >> np.uint64(64 - tail)).any()
 
 
+def test_running_best_tie_goes_to_the_first_iteration(G):
+    """130 iterations: the same failing hypothesis 70 times, then the same winning one 60 times, so
+    iterations 70 .. 129 tie exactly. In the wave that looks for the running best, lane 6 holds
+    iteration 70 and lane 0 only iteration 128 as candidates: a tie decided by lane instead of by
+    index would answer 128."""
+    m, d, _, min_inliers, _ = job(64)
+    d = np.ascontiguousarray(np.concatenate([np.repeat(d[0:1], 70, 0), np.repeat(d[12:13], 60, 0)]))
+    want = R.ransac(m, d, 130, min_inliers, M.K, M.SIGMA2, M.TH2)
+    assert min_inliers == 10
+    assert (want[0]["n_inliers"][:70] == 0).all() and (want[0]["n_inliers"][70:130] == 32).all()
+    assert (want[0]["best"][:70] == -1).all() and (want[0]["best"][70:130] == 70).all()
+    assert want[5] == 60 and want[4][:3].tolist() == [70, 71, 72]
+    got = run_single(G, m, d, 130, min_inliers)
+    assert_rows_equal(got, want, 130)
+    assert len(got[4]) == 60 and np.array_equal(got[4], want[4][:60])
+
+
 def draws_for_samples(n, samples):
     """The draws that resolve to the given samples (searched with the Python swap-and-pop)."""
     want = {tuple(s) for s in samples}
