@@ -109,6 +109,16 @@ int slamgpu_debug_level_keys(slamgpu_ctx* ctx, int img, int level, int stage, ui
 int slamgpu_frame_stereo(slamgpu_ctx* ctx, const uint8_t* left, const uint8_t* right,
                          size_t step, const slamgpu_camera* cam);
 
+/* Replaces the monocular Frame ctor's hot part (frame.cpp:162-209): ExtractORB(0, image),
+ * UndistortKeyPoints when a distortion is set (slamgpu_set_distortion), u_right / depth = -1 for
+ * every keypoint (:194-195) and AssignFeaturesToGrid. Results stay in the context as frame 0
+ * (image 0), as slamgpu_frame_stereo's do: slamgpu_download_keypoints(0), _download_stereo(0),
+ * _download_undistorted_keypoints(0) and the search calls (slamgpu_search_by_projection_* with
+ * mono = 1, slamgpu_search_for_initialization) work on it. cam->bf is not read by this call. A
+ * frame without keypoints is valid: searches on it find nothing. */
+int slamgpu_frame_mono(slamgpu_ctx* ctx, const uint8_t* img, size_t step,
+                       const slamgpu_camera* cam);
+
 /* Batched device path: n_frames stereo pairs already in device memory. Left view of frame f at
  * d_left + f * frame_stride, right view at d_right + f * frame_stride, `pitch` bytes per row.
  * Enqueues extraction of all 2n images, stereo matching and the 64x48 grid of every left view
@@ -297,6 +307,52 @@ int slamgpu_search_by_projection_reloc_device(slamgpu_ctx* ctx, const slamgpu_re
                                               int64_t mp_stride, int* d_nmatches, int n_frames,
                                               void* stream);
 
+/* ---- OrbMatcher::SearchForInitialization (orb_matcher.cpp:264-382) -------------------------- */
+/* Keypoint i1 of the initial frame F1: every keypoint of F1 is passed, so the query index is i1.
+ * 64 bytes. */
+typedef struct {
+  float angle;        /* F1.GetUndistortedKeys()[i1].angle                                     */
+  int32_t octave;     /* F1.GetUndistortedKeys()[i1].octave (a query above level 0 is skipped) */
+  int32_t pad[6];
+  uint8_t desc[32];   /* F1.GetDescriptors().row(i1)                                           */
+} slamgpu_init_query;
+
+typedef struct {
+  float nnratio;       /* mfNNratio (finite)                                                   */
+  int32_t window_size; /* windowSize >= 0: the window's half side is (float)windowSize         */
+  int32_t check_ori;   /* mbCheckOrientation                                                   */
+  int32_t pad;
+} slamgpu_init_search; /* 16 bytes */
+
+/* F2 is frame `frame` of the last frontend/frame call (its undistorted keypoints, descriptors
+ * and grid). prev_matched[n1][2] is vbPrevMatched, in/out: entry i1 is the window centre of query
+ * i1 and, for a match that survives the call, receives F2's undistorted keypoint position (every
+ * other entry is left as it came). matches12[n1] receives vnMatches12, *nmatches the return
+ * value (== the number of matches12 >= 0). Queries are resolved strictly in i1 order with the
+ * reference's rules: a keypoint of F2 matched at distance d is skipped by a later query at
+ * distance >= d (neither best nor second) and taken over at a smaller one; accepted iff
+ * bestDist <= 50 and bestDist < (float)bestDist2 * nnratio; taken-over matches stay counted in
+ * the rotation histogram. A prev_matched entry that is not finite (undefined behaviour in the
+ * reference: float -> int of NaN / infinity in GetFeaturesInArea) makes its query match nothing;
+ * its neighbours are unaffected. Errors (SLAMGPU_EINVAL with a message, nothing written): a null
+ * pointer, frame out of range, n1 < 0, window_size < 0, a non-finite nnratio. */
+int slamgpu_search_for_initialization(slamgpu_ctx* ctx, int frame,
+                                      const slamgpu_init_query* queries, int n1,
+                                      const slamgpu_init_search* params, float* prev_matched,
+                                      int32_t* matches12, int* nmatches);
+/* Batched over the frames of the last frontend call: frame f's queries are
+ * d_queries[d_q_start[f] .. + d_q_count[f]), d_prev_matched ([.][2]) and d_matches12 are parallel
+ * to d_queries, one parameter record per frame. The entries inside a frame's query range are
+ * written as above, everything outside is untouched. Never allocates and never synchronises:
+ * total_queries beyond max_frames * kp_cap (the workspace the context is created with) is
+ * SLAMGPU_ECAP. The parameters are read on the device, so their ranges are the caller's to keep. */
+int slamgpu_search_for_initialization_device(slamgpu_ctx* ctx, const slamgpu_init_query* d_queries,
+                                             int total_queries, const int* d_q_start,
+                                             const int* d_q_count, int max_queries,
+                                             const slamgpu_init_search* d_params,
+                                             float* d_prev_matched, int32_t* d_matches12,
+                                             int* d_nmatches, int n_frames, void* stream);
+
 /* Builds frame-to-frame queries on the device from the last frontend call: for frame f >= 1,
  * every left keypoint of frame f-1 with stereo depth becomes a map point at
  * Frame::UnprojectStereo(i) (frame.cpp:594-607) under d_poses[f-1] -- the visual-odometry points
@@ -312,7 +368,7 @@ int slamgpu_make_vo_queries_device(slamgpu_ctx* ctx, const slamgpu_f2f_pose* d_p
 /* Brackets every launch of `kernel` ("*" = all kernels) with HIP events on its stream until
  * slamgpu_timing_stop; slamgpu_timing_read sums the recorded durations. Kernel names: pyr_down,
  * blur7, fast_cells, octree, orient_desc, stereo_rows, stereo_match, stereo_median, grid_build,
- * vo_queries, search_cand, search_resolve. */
+ * vo_queries, search_cand, search_resolve, init_resolve. */
 int slamgpu_timing_start(slamgpu_ctx* ctx, const char* kernel, int max_launches);
 /* Batches run level 0's FAST on a side stream beside the pyramid (the default, on = 1); on = 0
  * runs it after the pyramid on the call's stream, so that a timing pass sees each kernel alone.
@@ -332,5 +388,7 @@ int slamgpu_trace_marker(int id, void* stream);
 static_assert(sizeof(slamgpu_reloc_query) == 64, "slamgpu_reloc_query is 64 bytes");
 static_assert(sizeof(slamgpu_reloc_pose) == 72 && sizeof(slamgpu_reloc_pose) % 8 == 0,
               "slamgpu_reloc_pose is 72 bytes");
+static_assert(sizeof(slamgpu_init_query) == 64, "slamgpu_init_query is 64 bytes");
+static_assert(sizeof(slamgpu_init_search) == 16, "slamgpu_init_search is 16 bytes");
 #endif
 #endif /* SLAMGPU_H_ */

@@ -1878,4 +1878,42 @@ inline int relocalization_refine(slamgpu_ctx* ctx, int frame, const slamgpu_came
   return nGood;
 }
 
+// ---- OrbMatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+// (orb_matcher.cpp:264-382), Tracker::MonocularInitialization (tracker.cpp:297-364). F2 is the
+// frame the context holds (slamgpu_frame_mono); F1 is the initial frame the caller kept.
+
+// One query per keypoint of F1, in keypoint order (the query index is i1): the undistorted
+// keypoint's angle and octave and descriptor row i1. FrameView carries no descriptors, so they
+// come beside it (F1.GetDescriptors(), n_kps x 32 bytes).
+inline std::vector<slamgpu_init_query> gather_search_for_initialization(const FrameView& F1,
+                                                                        const uint8_t* descriptors) {
+  std::vector<slamgpu_init_query> q(F1.n_kps > 0 ? F1.n_kps : 0);
+  for (int i = 0; i < F1.n_kps; ++i) {
+    std::memset(&q[i], 0, sizeof q[i]);
+    q[i].angle = F1.undist_kps[i].angle;
+    q[i].octave = F1.undist_kps[i].octave;
+    std::memcpy(q[i].desc, descriptors + (size_t)i * 32, 32);
+  }
+  return q;
+}
+
+// The whole call: prev_matched ([n1][2], vbPrevMatched) is in/out, matches12 ([n1], vnMatches12)
+// out. Returns nmatches; throws on an error.
+inline int search_for_initialization(slamgpu_ctx* ctx, int frame, const FrameView& F1,
+                                     const uint8_t* descriptors, float* prev_matched,
+                                     int32_t* matches12, int window_size, float nnratio,
+                                     bool check_ori) {
+  const std::vector<slamgpu_init_query> q = gather_search_for_initialization(F1, descriptors);
+  slamgpu_init_search p;
+  std::memset(&p, 0, sizeof p);
+  p.nnratio = nnratio;
+  p.window_size = window_size;
+  p.check_ori = check_ori ? 1 : 0;
+  int nm = 0;
+  const int rc = slamgpu_search_for_initialization(ctx, frame, q.data(), (int)q.size(), &p,
+                                                   prev_matched, matches12, &nm);
+  if (rc != SLAMGPU_OK) throw std::runtime_error(std::string("slamgpu: ") + slamgpu_last_error(ctx));
+  return nm;
+}
+
 }  // namespace slamgpu_adapter

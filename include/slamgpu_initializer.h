@@ -4,8 +4,8 @@
  *   Initializer::Initialize / FindHomography / FindFundamental / ReconstructH / ReconstructF /
  *   CheckRT / Triangulate / DecomposeE / Normalize                src/util/initializer.cpp:22-944
  * as Tracker::MonocularInitialization drives it (src/core/tracker.cpp:297-343) on every frame
- * until a map exists. vMatches12 comes from wherever the caller has it
- * (OrbMatcher::SearchForInitialization is not part of this library).
+ * until a map exists. vMatches12 is OrbMatcher::SearchForInitialization's output: on the device,
+ * slamgpu_search_for_initialization (slamgpu.h) on the frame slamgpu_frame_mono left in the context.
  *
  * The 2 x n_its hypotheses depend only on their draws, the best of a model is a prefix maximum
  * under strict >, and the 4 or 8 motion hypotheses of the chosen model do not depend on one

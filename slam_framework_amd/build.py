@@ -44,6 +44,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_pnpsolver_adapter_check()
         build_initializer_adapter_check()
         build_reloc_adapter_check()
+        build_initmatch_adapter_check()
         build_device_math_check()
         return LIB
     objdir = os.path.join(PKG, "build")
@@ -77,6 +78,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_pnpsolver_adapter_check()
     build_initializer_adapter_check()
     build_reloc_adapter_check()
+    build_initmatch_adapter_check()
     build_device_math_check()
     return LIB
 
@@ -194,6 +196,25 @@ def build_reloc_adapter_check() -> str:
                     "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", RELOC_ADAPTER_BIN],
                    check=True)
     return RELOC_ADAPTER_BIN
+
+
+INITMATCH_ADAPTER_SRC = os.path.join(ROOT, "tests", "initmatch_adapter_check.cpp")
+INITMATCH_ADAPTER_BIN = os.path.join(ROOT, "tests", "initmatch_adapter_check")
+
+
+def build_initmatch_adapter_check() -> str:
+    """g++ build of tests/initmatch_adapter_check.cpp: slamgpu_frame_mono and
+    search_for_initialization of include/slamgpu_adapters.hpp (the first two calls of
+    Tracker::MonocularInitialization, tracker.cpp:297-364) driven from C++ against libslamgpu.so."""
+    deps = [INITMATCH_ADAPTER_SRC, LIB] + glob.glob(os.path.join(ROOT, "include", "*.h*"))
+    if os.path.exists(INITMATCH_ADAPTER_BIN) and os.path.getmtime(INITMATCH_ADAPTER_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return INITMATCH_ADAPTER_BIN
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I",
+                    os.path.join(ROOT, "include"), INITMATCH_ADAPTER_SRC, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", INITMATCH_ADAPTER_BIN],
+                   check=True)
+    return INITMATCH_ADAPTER_BIN
 
 
 GEOMETRY_SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")

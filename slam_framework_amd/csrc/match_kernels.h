@@ -130,6 +130,24 @@ struct RelocPose {
 };
 static_assert(sizeof(RelocPose) == 72, "RelocPose layout");
 
+// One query of OrbMatcher::SearchForInitialization (orb_matcher.cpp:264-382): keypoint i1 of the
+// initial frame F1 (all of them are passed: the query index is i1).
+struct InitQuery {
+  float angle;         // F1.GetUndistortedKeys()[i1].angle
+  int octave;          // ... .octave (a query above level 0 is skipped, :283-285)
+  int pad[6];
+  uint8_t desc[32];    // F1.GetDescriptors().row(i1)
+};
+static_assert(sizeof(InitQuery) == 64, "InitQuery layout");
+
+struct InitSearch {
+  float nnratio;       // OrbMatcher::mfNNratio
+  int window_size;     // windowSize: the search square's half side, (float)windowSize
+  int check_ori;       // OrbMatcher::mbCheckOrientation
+  int pad;
+};
+static_assert(sizeof(InitSearch) == 16, "InitSearch layout");
+
 struct MatchWorkspace {
   uint64_t* topk;      // [query][kTopK] (dist, grid order) keys
   int* ncand;          // [query]
@@ -145,6 +163,15 @@ struct MatchIO {
                        // (relocalisation search: slot holds a map point)
   int* nmatches;       // [frame]
   int64_t mp_stride;   // stride of map_point/blocked between frames (keypoints)
+};
+
+// SearchForInitialization's arrays, parallel to the queries (query q of the call's list).
+struct InitIO {
+  const int* q_start;  // [frame] first query of the frame
+  const int* q_count;  // [frame]
+  float* prev_matched;  // [query][2] in/out: vbPrevMatched (the window centre; the match's pt)
+  int* matches12;      // [query] out: vnMatches12
+  int* nmatches;       // [frame]
 };
 
 void launch_grid(const FrameKps& cur, const Camera& cam, int n_frames, int kp_cap,
@@ -173,6 +200,13 @@ void launch_search_reloc(const FrameKps& cur, const float* u_right, int64_t ur_s
                          const RelocPose* poses, int n_frames, int max_queries_per_frame,
                          const GridWorkspace& gw, const MatchWorkspace& mw, const MatchIO& io,
                          hipStream_t st);
+
+// SearchForInitialization of every frame's query list against the frame's keypoints: the
+// candidate scan (search_cand, 64 lanes per query), then init_resolve, one wave per frame.
+void launch_search_init(const FrameKps& cur, const Camera& cam, const OrbGeomDev& g,
+                        const InitQuery* queries, const InitSearch* params, int n_frames,
+                        int max_queries_per_frame, const GridWorkspace& gw,
+                        const MatchWorkspace& mw, const InitIO& io, hipStream_t st);
 
 // Queries for frame f from frame f-1's stereo keypoints (frame 0 gets none); queries of frame f
 // occupy queries[f * kp_cap ...].

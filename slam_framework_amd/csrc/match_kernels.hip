@@ -776,6 +776,7 @@ struct ScanCtx {
   float ur, gate;        // skip if u_right > 0 && fabsf(ur - u_right) > gate
   int max_dist;          // keep candidates with distance <= max_dist
   const uint8_t* desc;   // query descriptor
+  float nnratio;         // SearchForInitialization's filter only (see scan_query_k)
 };
 
 struct FrameView {
@@ -809,7 +810,13 @@ __device__ __forceinline__ uint64_t key64(K k) {
 // search_cand (a window holds a handful of keypoints: four queries per wave keep the lanes busy)
 // skip: the group has no query (or its context failed): it scans nothing -- no cell bound is
 // derived from its coordinates -- but still takes part in the group's shuffles and the merge
-template <typename K, int G = 64>
+// kInit: SearchForInitialization's per-candidate filter in place of the projection searches'
+// three (no slot state, no right coordinate): `claimed` is then the vMatchedDistance table (ints,
+// INT_MAX = unmatched; null in search_cand) and a candidate with table[i] <= dist is skipped
+// (:306-307). Candidates that can never matter are dropped too: one above TH_LOW never is an
+// accepted best, and as a second with (float)dist * nnratio > TH_LOW it passes every best the
+// ratio test can see (:321-323), as the seconds behind it and an absent second (INT_MAX) do.
+template <typename K, int G = 64, bool kInit = false>
 __device__ int scan_query_k(const ScanCtx& c, const Camera& cam, const FrameView& F,
                             const uint32_t* claimed, uint64_t* top, int lane, bool skip = false) {
   const int gl = lane & (G - 1), gb = lane & ~(G - 1);
@@ -865,14 +872,21 @@ __device__ int scan_query_k(const ScanCtx& c, const Camera& cam, const FrameView
         }
         const float distx = __uint_as_float(it.y) - c.x, disty = __uint_as_float(it.z) - c.y;
         if (!(fabsf(distx) < c.r && fabsf(disty) < c.r)) continue;
-        // the remaining filters' loads all in flight together (the filters commute)
-        const bool blk = F.blocked[i] != 0;
-        const float ur = F.u_right[i];
-        const int dist = hamming32(c.desc, F.desc + i * 32);
-        if (blk) continue;
-        if (claimed && (claimed[i >> 5] >> (i & 31)) & 1u) continue;
-        if (ur > 0 && fabsf(c.ur - ur) > c.gate) continue;
-        if (dist > c.max_dist) continue;
+        int dist;
+        if constexpr (kInit) {
+          dist = hamming32(c.desc, F.desc + i * 32);
+          if (claimed && (int)claimed[i] <= dist) continue;
+          if (dist > kThLow && (float)dist * c.nnratio > (float)kThLow) continue;
+        } else {
+          // the remaining filters' loads all in flight together (the filters commute)
+          const bool blk = F.blocked[i] != 0;
+          const float ur = F.u_right[i];
+          dist = hamming32(c.desc, F.desc + i * 32);
+          if (blk) continue;
+          if (claimed && (claimed[i >> 5] >> (i & 31)) & 1u) continue;
+          if (ur > 0 && fabsf(c.ur - ur) > c.gate) continue;
+          if (dist > c.max_dist) continue;
+        }
         const K key = scan_key<K>(dist, pcell, i);
         cnt++;
         if (key < t[kTopK - 1]) {
@@ -914,12 +928,12 @@ __device__ int scan_query_k(const ScanCtx& c, const Camera& cam, const FrameView
 
 // 32-bit keys whenever the frame's keypoint indices fit 11 bits (kp_cap <= 2048: nfeatures up to
 // ~2000 with the per-level slack), the 64-bit form otherwise.
-template <int G = 64>
+template <int G = 64, bool kInit = false>
 __device__ __forceinline__ int scan_query(const ScanCtx& c, const Camera& cam, const FrameView& F,
                                           const uint32_t* claimed, uint64_t* top, int lane,
                                           int kp_cap, bool skip = false) {
-  if (kp_cap <= 2048) return scan_query_k<uint32_t, G>(c, cam, F, claimed, top, lane, skip);
-  return scan_query_k<uint64_t, G>(c, cam, F, claimed, top, lane, skip);
+  if (kp_cap <= 2048) return scan_query_k<uint32_t, G, kInit>(c, cam, F, claimed, top, lane, skip);
+  return scan_query_k<uint64_t, G, kInit>(c, cam, F, claimed, top, lane, skip);
 }
 
 // SearchByProjection(CurrentFrame, LastFrame) per-query setup (orb_matcher.cpp:1336-1376).
@@ -1011,6 +1025,27 @@ __device__ bool reloc_ctx(const RelocQuery& q, const RelocPose& P, const Camera&
   return true;
 }
 
+// SearchForInitialization per-query setup (orb_matcher.cpp:282-287): no projection -- the window
+// is GetFeaturesInArea(vbPrevMatched[i1], windowSize, level1, level1) for a level-0 keypoint.
+// Where the reference's arithmetic is undefined (a vbPrevMatched entry that is not finite: float
+// -> int of NaN / inf in GetFeaturesInArea) the query matches nothing.
+__device__ bool init_ctx(const InitQuery& q, float2 prev, const InitSearch& P, ScanCtx* c) {
+  const int level1 = q.octave;
+  if (level1 > 0) return false;
+  if (!isfinite(prev.x) || !isfinite(prev.y)) return false;
+  c->x = prev.x;
+  c->y = prev.y;
+  c->r = (float)P.window_size;
+  c->min_level = level1;
+  c->max_level = level1;
+  c->ur = 0.0f;
+  c->gate = __builtin_huge_valf();
+  c->max_dist = 256;
+  c->desc = q.desc;
+  c->nnratio = P.nnratio;
+  return true;
+}
+
 // The per-frame pose record of a query type (the local-map search has none).
 template <typename Q>
 struct SearchPose {
@@ -1021,6 +1056,21 @@ struct SearchPose<RelocQuery> {
   using type = RelocPose;
 };
 
+template <>
+struct SearchPose<InitQuery> {
+  using type = InitSearch;
+};
+
+// The caller's arrays of a query type's search.
+template <typename Q>
+struct SearchIO {
+  using type = MatchIO;
+};
+template <>
+struct SearchIO<InitQuery> {
+  using type = InitIO;
+};
+
 // The per-query setup of the query type's overload.
 template <typename Q>
 __device__ __forceinline__ bool make_ctx(const Q& q, const typename SearchPose<Q>::type* poses,
@@ -1029,6 +1079,20 @@ __device__ __forceinline__ bool make_ctx(const Q& q, const typename SearchPose<Q
   if constexpr (std::is_same<Q, F2FQuery>::value) return f2f_ctx(q, poses[f], cam, g, c);
   else if constexpr (std::is_same<Q, RelocQuery>::value) return reloc_ctx(q, poses[f], cam, g, c);
   else return mps_ctx(q, th, g, c);
+}
+
+// SearchForInitialization reads neither u_right nor the slot state
+__device__ __forceinline__ FrameView frame_view(int f, const FrameKps& cur, const float*,
+                                                int64_t, const GridWorkspace& gw, const InitIO&,
+                                                int kp_cap) {
+  FrameView F;
+  F.kps = cur.kps + f * cur.stride;
+  F.desc = cur.desc + f * cur.stride * 32;
+  F.u_right = nullptr;
+  F.cell_start = gw.cell_start + (int64_t)f * (kGridCells + 1);
+  F.cell_items = gw.cell_items + (int64_t)f * kp_cap;
+  F.blocked = nullptr;
+  return F;
 }
 
 __device__ __forceinline__ FrameView frame_view(int f, const FrameKps& cur, const float* u_right,
@@ -1048,27 +1112,38 @@ __device__ __forceinline__ FrameView frame_view(int f, const FrameKps& cur, cons
 #define SEARCH_LANES 16
 #endif
 constexpr int kSearchG = SEARCH_LANES;  // lanes per query in search_cand (16 or 64)
+// SearchForInitialization's window (windowSize 100: 200 x 200 px, some 300 grid cells and a few
+// hundred keypoints of all levels, against a handful in the projection searches) is walked 64
+// lanes wide: a quarter of the dependent cell / pair rounds per query, and its level-0 queries
+// (some 440 to 870 waves) still fill the device.
+template <typename Q>
+constexpr int kSearchLanes = std::is_same<Q, InitQuery>::value ? 64 : kSearchG;
 template <typename Q>
 __global__ __launch_bounds__(256) void search_cand_kernel(
     FrameKps cur, const float* __restrict__ u_right, int64_t ur_stride, Camera cam,
     const OrbGeom* __restrict__ g, const Q* __restrict__ queries,
     const typename SearchPose<Q>::type* __restrict__ poses, int th, GridWorkspace gw,
-    MatchWorkspace mw, MatchIO io) {
+    MatchWorkspace mw, typename SearchIO<Q>::type io) {
+  constexpr bool kInit = std::is_same<Q, InitQuery>::value;
+  constexpr int kG = kSearchLanes<Q>;
   int f, bx;
   xcd_image_block(&f, &bx);  // a frame's work-groups share one XCD's L2 (its grid and keypoints)
-  // kSearchG lanes per query: 64 / kSearchG queries per wave
-  const int lane = threadIdx.x & 63, gl = lane & (kSearchG - 1);
-  const int qi = (bx * 4 + wave_id()) * (64 / kSearchG) + lane / kSearchG;
+  // kG lanes per query: 64 / kG queries per wave
+  const int lane = threadIdx.x & 63, gl = lane & (kG - 1);
+  const int qi = (bx * 4 + wave_id()) * (64 / kG) + lane / kG;
   const int qcount = io.q_count[f];
-  if (__builtin_amdgcn_readfirstlane((bx * 4 + wave_id()) * (64 / kSearchG)) >= qcount) return;
+  if (__builtin_amdgcn_readfirstlane((bx * 4 + wave_id()) * (64 / kG)) >= qcount) return;
   const bool live = qi < qcount;  // the wave's last groups may have no query
   const int q = io.q_start[f] + (live ? qi : 0);
   const FrameView F = frame_view(f, cur, u_right, ur_stride, gw, io, g->kp_cap);
   ScanCtx c;
-  const bool ok = make_ctx(queries[q], poses, f, th, cam, g, &c) && live;
+  bool ok;
+  if constexpr (kInit) ok = init_ctx(queries[q], make_float2(io.prev_matched[2 * q], io.prev_matched[2 * q + 1]),
+                                   poses[f], &c) && live;
+  else ok = make_ctx(queries[q], poses, f, th, cam, g, &c) && live;
   uint64_t top[kTopK];
   // a group without a query scans nothing but takes part in the merge
-  const int n = scan_query<kSearchG>(c, cam, F, nullptr, top, lane, g->kp_cap, !ok);
+  const int n = scan_query<kG, kInit>(c, cam, F, nullptr, top, lane, g->kp_cap, !ok);
   if (live && gl < kTopK) {
     uint64_t v = top[0];
 #pragma unroll
@@ -1334,6 +1409,214 @@ __global__ __launch_bounds__(64) void search_resolve_kernel(
     }
   }
   if (lane == 0) io.nmatches[f] = nm;
+}
+
+// SearchForInitialization's in-order loop (orb_matcher.cpp:280-349) and its tail (:351-379): one
+// wave per frame. A match here carries its distance and can be taken over by a later query with
+// a strictly smaller one (:306-307, :325-333), so the state per keypoint of F2 is
+// vMatchedDistance and vnMatches21, both in LDS (kp_cap <= 4096), and per query the keypoint it
+// matched when it was accepted (s_best; queries past kResolveLdsQ use the workspace). 64 queries
+// (one per lane) are decided together against the committed tables from their kept candidates: a
+// kept candidate i2 is eligible iff vMatchedDistance[i2] > dist, the first two eligible ones in
+// (distance, GetFeaturesInArea order) are bestDist / bestDist2. Accepting lanes stamp their
+// keypoint with the lowest such lane; the first lane that needs a rescan, or that has a kept
+// candidate stamped by a lower lane (its decision may change once that lane commits), ends the
+// round: the lanes below it commit -- no two of them share a keypoint, each has the other's in
+// its kept list or not at all -- and the round restarts there. A query whose kept list runs out
+// before the decision is known is rescanned alone at its place in the order, the live
+// vMatchedDistance table as the scan's filter.
+// vnMatches12 is not kept while the loop runs: query i1 holds its match at the end iff
+// vnMatches21[s_best[i1]] == i1 (a query is accepted once, a take-over rewrites vnMatches21).
+// The rotation bins are taken after the loop from s_best, taken-over entries included (:344: the
+// entry is never removed), and the removal loop clears only matches that still hold (:366).
+__global__ __launch_bounds__(64) void init_resolve_kernel(
+    FrameKps cur, Camera cam, const OrbGeom* __restrict__ g, const InitQuery* __restrict__ queries,
+    const InitSearch* __restrict__ params, GridWorkspace gw, MatchWorkspace mw, InitIO io) {
+  __shared__ int matched_dist[4096];  // vMatchedDistance
+  __shared__ int matches21[4096];     // vnMatches21
+  __shared__ int stamp[4096];         // lowest lane of the round that accepts the keypoint
+  __shared__ int hist[kHisto];
+  __shared__ int16_t s_best[kResolveLdsQ];  // keypoint query qi matched at accept time (-1 none)
+  __shared__ int8_t s_bin[kResolveLdsQ];    // its rotation bin
+  const int f = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int kp_cap = g->kp_cap;
+  const int n = min(cur.n[f * cur.n_stride], 4096);
+  for (int i = lane; i < n; i += 64) {
+    matched_dist[i] = INT_MAX;
+    matches21[i] = -1;
+    stamp[i] = INT_MAX;
+  }
+  if (lane < kHisto) hist[lane] = 0;
+  const FrameView F = frame_view(f, cur, nullptr, 0, gw, io, kp_cap);
+  const InitSearch P = params[f];
+  const float nnratio = P.nnratio;
+  const bool check_ori = P.check_ori != 0;
+  const int q0 = io.q_start[f], qn = io.q_count[f];
+  auto set_best = [&](int qi, int idx) {
+    if (qi < kResolveLdsQ) s_best[qi] = (int16_t)idx;
+    else mw.best_idx[q0 + qi] = idx;
+  };
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  auto get_best = [&](int qi) {
+    return qi < kResolveLdsQ ? (int)s_best[qi] : mw.best_idx[q0 + qi];
+  };
+  // :321-323 -- int against float, the product in float, bestDist2 possibly INT_MAX
+  auto accepts = [&](int bestDist, int bestDist2) {
+    return bestDist <= kThLow && (float)bestDist < (float)bestDist2 * nnratio;
+  };
+  struct QIn {
+    uint64_t key[kTopK];
+    int nc;
+  };
+  auto load_chunk = [&](int c0, QIn& in) {
+    const int qi = c0 + lane;
+#pragma unroll
+    for (int k = 0; k < kTopK; k++)
+      in.key[k] = qi < qn ? mw.topk[(int64_t)(q0 + qi) * kTopK + k] : kNoKey;
+    in.nc = qi < qn ? mw.ncand[q0 + qi] : 0;
+  };
+  QIn nx;
+  load_chunk(0, nx);
+  for (int c0 = 0; c0 < qn; c0 += 64) {
+    const int qi = c0 + lane;
+    const bool valid = qi < qn;
+    const QIn in = nx;
+    if (c0 + 64 < qn) load_chunk(c0 + 64, nx);  // in flight while this chunk resolves
+    const uint64_t* key = in.key;
+    const int nc = in.nc;
+    if (valid) set_best(qi, -1);
+    int start = 0;
+    while (start < 64 && c0 + start < qn) {
+      const bool act = valid && lane >= start && nc > 0;
+      // -- every lane's decision against the committed tables
+      int d1 = INT_MAX, d2 = INT_MAX, i1 = -1, nel = 0, dlast = 0;
+      if (act) {
+#pragma unroll
+        for (int k = 0; k < kTopK; k++) {
+          if (key[k] == kNoKey) continue;
+          const int d = key_dist(key[k]), idx = key_idx(key[k]);
+          dlast = d;
+          if (matched_dist[idx] <= d) continue;
+          if (nel == 0) {
+            d1 = d;
+            i1 = idx;
+          } else if (nel == 1) {
+            d2 = d;
+          }
+          nel++;
+        }
+      }
+      // the kept list decides unless more candidates exist behind it and it holds no eligible
+      // one, or a best within TH_LOW without a second -- and then still decides when the best
+      // passes the ratio test against the last kept distance (a second behind the list is no
+      // nearer; nnratio >= 0 keeps the product monotonic)
+      bool rescan = false;
+      if (act && nc > kTopK) {
+        if (nel == 0) rescan = true;
+        else if (nel == 1 && d1 <= kThLow)
+          rescan = !(nnratio >= 0.0f && (float)d1 < (float)dlast * nnratio);
+      }
+      const bool acc = act && !rescan && nel > 0 && accepts(d1, d2);
+      if (acc) atomicMin(&stamp[i1], lane);
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      bool conflict = false;
+      if (act) {
+#pragma unroll
+        for (int k = 0; k < kTopK; k++)
+          if (key[k] != kNoKey && stamp[key_idx(key[k])] < lane) conflict = true;
+      }
+      const uint64_t stop = __ballot(rescan || conflict);
+      const int r = stop ? __ffsll((long long)stop) - 1 : 64;
+      const bool r_conflict = r < 64 && ((__ballot(conflict) >> r) & 1ull);
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (acc) stamp[i1] = INT_MAX;
+      if (acc && lane < r) {  // :325-333
+        matched_dist[i1] = d1;
+        matches21[i1] = qi;
+        set_best(qi, i1);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (r < 64 && !r_conflict) {
+        // lane r: rescanned alone, the candidates vMatchedDistance excludes left out by the scan
+        const int qr = q0 + c0 + r;
+        ScanCtx c;
+        const bool okc = init_ctx(
+            queries[qr], make_float2(io.prev_matched[2 * qr], io.prev_matched[2 * qr + 1]), P, &c);
+        uint64_t top[kTopK];
+        if (okc)
+          scan_query<64, true>(c, cam, F, reinterpret_cast<const uint32_t*>(matched_dist), top,
+                               lane, kp_cap);
+        const uint64_t t1 = okc ? top[0] : kNoKey, t2 = okc ? top[1] : kNoKey;
+        if (lane == r && t1 != kNoKey &&
+            accepts(key_dist(t1), t2 == kNoKey ? INT_MAX : key_dist(t2))) {
+          const int idx = key_idx(t1);
+          matched_dist[idx] = key_dist(t1);
+          matches21[idx] = qi;
+          set_best(qi, idx);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        start = r + 1;
+      } else {
+        start = r;  // 64, or a lane to decide again against the tables as they are now
+      }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // -- rotation histogram (:335-345) of every accepted query, then the tail
+  if (check_ori) {
+    for (int qi = lane; qi < qn; qi += 64) {
+      const int idx = get_best(qi);
+      int bin = -1;
+      if (idx >= 0) {
+        bin = rot_bin(queries[q0 + qi].angle, F.kps[idx].angle);
+        atomicAdd(&hist[bin], 1);
+      }
+      if (qi < kResolveLdsQ) s_bin[qi] = (int8_t)bin;
+      else mw.rot_bin[q0 + qi] = bin;
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  int ind1 = -1, ind2 = -1, ind3 = -1;
+  if (check_ori) three_maxima(hist, &ind1, &ind2, &ind3);
+  int nm = 0;
+  for (int qi = lane; qi < qn; qi += 64) {
+    const int idx = get_best(qi);
+    bool holds = idx >= 0 && matches21[idx] == qi;
+    if (holds && check_ori) {
+      const int bin = qi < kResolveLdsQ ? (int)s_bin[qi] : mw.rot_bin[q0 + qi];
+      if (bin != ind1 && bin != ind2 && bin != ind3) holds = false;  // :359-372
+    }
+    io.matches12[q0 + qi] = holds ? idx : -1;
+    if (holds) {  // :377-379
+      const KeyPoint& kp = F.kps[idx];
+      io.prev_matched[2 * (q0 + qi)] = kp.x;
+      io.prev_matched[2 * (q0 + qi) + 1] = kp.y;
+      nm++;
+    }
+  }
+  nm = wave_sum(nm);
+  if (lane == 0) io.nmatches[f] = nm;
+}
+
+void launch_search_init(const FrameKps& cur, const Camera& cam, const OrbGeomDev& g,
+                        const InitQuery* queries, const InitSearch* params, int n_frames,
+                        int max_q, const GridWorkspace& gw, const MatchWorkspace& mw,
+                        const InitIO& io, hipStream_t st) {
+  constexpr int kPerBlock = 4 * (64 / kSearchLanes<InitQuery>);
+  if (max_q > 0)
+    SLAMGPU_LAUNCH("search_cand", st, search_cand_kernel<InitQuery>,
+                   dim3((max_q + kPerBlock - 1) / kPerBlock, n_frames), dim3(256), 0, st, cur,
+                   (const float*)nullptr, (int64_t)0, cam, g.dev, queries, params, 0, gw, mw, io);
+  SLAMGPU_LAUNCH("init_resolve", st, init_resolve_kernel, dim3(n_frames), dim3(64), 0, st, cur,
+                 cam, g.dev, queries, params, gw, mw, io);
 }
 
 // The candidate search of every frame's queries, then the in-order claim resolution.

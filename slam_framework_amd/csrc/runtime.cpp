@@ -686,6 +686,33 @@ int slamgpu_frame_stereo(slamgpu_ctx* c, const uint8_t* left, const uint8_t* rig
   return 0;
 }
 
+// The monocular Frame ctor (frame.cpp:162-209) as plain launches on the context's stream: the
+// extraction of image 0, UndistortKeyPoints, u_right / depth = -1 (:194-195), the grid.
+int slamgpu_frame_mono(slamgpu_ctx* c, const uint8_t* img, size_t step, const slamgpu_camera* cam) {
+  if (!c || !img || !cam) return SLAMGPU_EINVAL;
+  HIPCHECK(c->err, hipSetDevice(c->device));
+  set_camera(c, cam);
+  if (int r = stage_images(c, &img, 1, step)) return r;
+  ImageBatch b{c->d_in, c->d_in + c->in_stride, 2 * c->in_stride, c->in_pitch, c->d_pyr};
+  if (int rc = run_frontend(c, b, 1, 1, false, c->stream)) return rc;
+  TimerScope ts(c);
+  const int64_t kc = c->geom.kp_cap;
+  if (c->dist_on)
+    launch_undistort(FrameKps{c->out.kps, c->out.desc, c->out.nkps, 2 * kc, 2}, c->kps_un, 2 * kc,
+                     c->cam, c->dist, 1, c->geom.kp_cap, c->stream);
+  const float minus_one = -1.0f;
+  int bits;
+  std::memcpy(&bits, &minus_one, sizeof(bits));
+  HIPCHECK(c->err, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->sout.u_right), bits,
+                                     (size_t)kc, c->stream));
+  HIPCHECK(c->err, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->sout.depth), bits,
+                                     (size_t)kc, c->stream));
+  launch_grid(left_views(c), c->cam, 1, c->geom.kp_cap, c->gws, c->stream);
+  HIPCHECK(c->err, hipGetLastError());
+  HIPCHECK(c->err, hipStreamSynchronize(c->stream));
+  return check_device_err(c);
+}
+
 int slamgpu_frontend_device(slamgpu_ctx* c, const uint8_t* d_left, const uint8_t* d_right,
                             size_t frame_stride, size_t pitch, int n_frames,
                             const slamgpu_camera* cam, void* stream) {
@@ -1011,6 +1038,100 @@ int slamgpu_search_by_projection_reloc_device(slamgpu_ctx* c, const slamgpu_relo
                       reinterpret_cast<const RelocPose*>(d_poses), n_frames, max_queries, c->gws,
                       c->mws, io, pick_stream(c, stream));
   HIPCHECK(c->err, hipGetLastError());
+  return 0;
+}
+
+int slamgpu_search_for_initialization_device(slamgpu_ctx* c, const slamgpu_init_query* d_q,
+                                             int total_queries, const int* d_q_start,
+                                             const int* d_q_count, int max_queries,
+                                             const slamgpu_init_search* d_params,
+                                             float* d_prev_matched, int32_t* d_matches12,
+                                             int* d_nmatches, int n_frames, void* stream) {
+  if (!c) return SLAMGPU_EINVAL;
+  if (!c->have_cam || n_frames < 1 || n_frames > c->n_frames_last || total_queries < 0 ||
+      max_queries < 0 || (max_queries > 0 && (!d_q || !d_prev_matched || !d_matches12)) ||
+      !d_q_start || !d_q_count || !d_params || !d_nmatches)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization_device: bad arguments");
+  // never allocates: the workspace holds max_frames * kp_cap queries from creation on
+  if (total_queries > c->mw_cap)
+    return slot(c).fail(SLAMGPU_ECAP,
+                        "search_for_initialization_device: %d queries, the workspace holds %d",
+                        total_queries, c->mw_cap);
+  InitIO io{d_q_start, d_q_count, d_prev_matched, d_matches12, d_nmatches};
+  TimerScope ts(c);
+  launch_search_init(left_views(c), c->cam, c->gd(), reinterpret_cast<const InitQuery*>(d_q),
+                     reinterpret_cast<const InitSearch*>(d_params), n_frames, max_queries, c->gws,
+                     c->mws, io, pick_stream(c, stream));
+  HIPCHECK(c->err, hipGetLastError());
+  return 0;
+}
+
+// The host form: F1's queries, the parameters, vbPrevMatched and vnMatches12 staged in the
+// query buffer host_search uses, one frame's view, one synchronisation.
+int slamgpu_search_for_initialization(slamgpu_ctx* c, int frame, const slamgpu_init_query* q,
+                                      int n1, const slamgpu_init_search* params,
+                                      float* prev_matched, int32_t* matches12, int* nmatches) {
+  if (!c) return SLAMGPU_EINVAL;
+  if (!params || !nmatches || n1 < 0 || (n1 > 0 && (!q || !prev_matched || !matches12)))
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: null argument or n1 < 0");
+  if (!c->have_cam || frame < 0 || frame >= c->n_frames_last)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: frame %d outside [0, %d)",
+                        frame, c->n_frames_last);
+  if (params->window_size < 0)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: window_size %d < 0",
+                        params->window_size);
+  if (!std::isfinite(params->nnratio))
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: nnratio is not finite");
+  HIPCHECK(c->err, hipSetDevice(c->device));
+  const size_t nq = (size_t)std::max(n1, 1);
+  const size_t off_p = (sizeof(InitQuery) * nq + 255) / 256 * 256;
+  const size_t off_prev = off_p + 256, off_m = off_prev + (8 * nq + 255) / 256 * 256;
+  const size_t need = off_m + 4 * nq + 256;
+  if (need > c->qbuf_bytes) {
+    if (int rc = dalloc(c, reinterpret_cast<uint8_t**>(&c->d_qbuf), need)) return rc;
+    c->qbuf_bytes = need;
+  }
+  if (int rc = ensure_match_ws(c, n1)) return rc;
+  hipStream_t st = c->stream;
+  uint8_t* qb = static_cast<uint8_t*>(c->d_qbuf);
+  float* d_prev = reinterpret_cast<float*>(qb + off_prev);
+  int32_t* d_m12 = reinterpret_cast<int32_t*>(qb + off_m);
+  if (n1) {
+    HIPCHECK(c->err, hipMemcpyAsync(qb, q, sizeof(InitQuery) * n1, hipMemcpyHostToDevice, st));
+    HIPCHECK(c->err, hipMemcpyAsync(d_prev, prev_matched, 8 * (size_t)n1, hipMemcpyHostToDevice, st));
+  }
+  HIPCHECK(c->err, hipMemcpyAsync(qb + off_p, params, sizeof(InitSearch), hipMemcpyHostToDevice, st));
+  int meta[2] = {0, n1};
+  HIPCHECK(c->err, hipMemcpyAsync(c->d_qmeta, meta, sizeof(meta), hipMemcpyHostToDevice, st));
+  const int64_t kc = c->geom.kp_cap;
+  FrameKps cur{(c->dist_on ? c->kps_un : c->out.kps) + 2 * frame * kc,
+               c->out.desc + 2 * frame * kc * 32, c->out.nkps + 2 * frame, 2 * kc, 2};
+  GridWorkspace gw = c->gws;
+  gw.cell_start += (int64_t)frame * (kGridCells + 1);
+  gw.cell_items += (int64_t)frame * kc;
+  InitIO io{c->d_qmeta, c->d_qmeta + 1, d_prev, d_m12, c->d_nm};
+  {
+    TimerScope ts(c);
+    launch_search_init(cur, c->cam, c->gd(), reinterpret_cast<const InitQuery*>(qb),
+                       reinterpret_cast<const InitSearch*>(qb + off_p), 1, n1, gw, c->mws, io, st);
+  }
+  HIPCHECK(c->err, hipGetLastError());
+  // staged on the host side first: nothing is written unless the whole call succeeds
+  std::vector<float> h_prev(2 * (size_t)n1);
+  std::vector<int32_t> h_m12((size_t)n1);
+  if (n1) {
+    HIPCHECK(c->err, hipMemcpyAsync(h_prev.data(), d_prev, 8 * (size_t)n1, hipMemcpyDeviceToHost, st));
+    HIPCHECK(c->err, hipMemcpyAsync(h_m12.data(), d_m12, 4 * (size_t)n1, hipMemcpyDeviceToHost, st));
+  }
+  int nm = 0;
+  HIPCHECK(c->err, hipMemcpyAsync(&nm, c->d_nm, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHECK(c->err, hipStreamSynchronize(st));
+  if (int rc = check_device_err(c)) return rc;
+  if (n1) {
+    std::memcpy(prev_matched, h_prev.data(), 8 * (size_t)n1);
+    std::memcpy(matches12, h_m12.data(), 4 * (size_t)n1);
+  }
+  *nmatches = nm;
   return 0;
 }
 

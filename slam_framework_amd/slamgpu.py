@@ -40,6 +40,13 @@ RELOC_QUERY_DTYPE = np.dtype([("xyz", "<f4", (3,)), ("max_dist", "<f4"), ("min_d
 RELOC_POSE_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)),
                              ("th", "<f4"), ("orb_dist", "<i4"), ("check_ori", "<i4")])
 assert RELOC_QUERY_DTYPE.itemsize == 64 and RELOC_POSE_DTYPE.itemsize == 72
+# slamgpu_init_query / slamgpu_init_search (include/slamgpu.h): keypoint i1 of the initial frame
+# for SearchForInitialization, and the call's parameters.
+INIT_QUERY_DTYPE = np.dtype([("angle", "<f4"), ("octave", "<i4"), ("pad", "<i4", (6,)),
+                             ("desc", "u1", (32,))])
+INIT_SEARCH_DTYPE = np.dtype([("nnratio", "<f4"), ("window_size", "<i4"), ("check_ori", "<i4"),
+                              ("pad", "<i4")])
+assert INIT_QUERY_DTYPE.itemsize == 64 and INIT_SEARCH_DTYPE.itemsize == 16
 # slamgpu_sim3_match (include/slamgpu_optimizer.h): one OptimizeSim3 correspondence.
 SIM3_MATCH_DTYPE = np.dtype([("x1c", "<f4", (3,)), ("x2c", "<f4", (3,)), ("u1", "<f4"),
                              ("v1", "<f4"), ("u2", "<f4"), ("v2", "<f4"), ("octave1", "<i4"),
@@ -103,6 +110,8 @@ EXPORTS = [
     "slamgpu_search_by_projection_mps", "slamgpu_search_by_projection_frame_device",
     "slamgpu_search_by_projection_mps_device", "slamgpu_search_by_projection_reloc",
     "slamgpu_search_by_projection_reloc_device", "slamgpu_debug_level_keys",
+    "slamgpu_frame_mono", "slamgpu_search_for_initialization",
+    "slamgpu_search_for_initialization_device",
     "slamgpu_make_vo_queries_device", "slamgpu_timing_start", "slamgpu_timing_stop",
     "slamgpu_set_extract_fork",
     "slamgpu_trace_marker",
@@ -228,6 +237,12 @@ def lib():
                                                          C.POINTER(ip)]
         L.slamgpu_search_by_projection_reloc_device.argtypes = [
             vp, vp, ip, vp, vp, ip, vp, vp, vp, C.c_int64, vp, ip, vp]
+        if hasattr(L, "slamgpu_frame_mono"):  # absent from older A/B builds (SLAMGPU_LIB)
+            L.slamgpu_frame_mono.argtypes = [vp, vp, sz, C.POINTER(Camera)]
+            L.slamgpu_search_for_initialization.argtypes = [vp, ip, vp, ip, vp, vp, vp,
+                                                            C.POINTER(ip)]
+            L.slamgpu_search_for_initialization_device.argtypes = [
+                vp, vp, ip, vp, vp, ip, vp, vp, vp, vp, ip, vp]
         L.slamgpu_debug_level_keys.argtypes = [vp, ip, ip, ip, vp, ip, C.POINTER(ip)]
         L.slamgpu_make_vo_queries_device.argtypes = [vp, vp, ip, vp, vp, vp, ip, vp]
         L.slamgpu_timing_start.argtypes = [vp, C.c_char_p, ip]
@@ -394,6 +409,14 @@ class Context:
         self.check(lib().slamgpu_frame_stereo(self.h, _ptr(left), _ptr(right), left.strides[0],
                                               C.byref(self.cam)))
 
+    def frame_mono(self, img, cam):
+        """slamgpu_frame_mono: the monocular Frame ctor's hot part; the image's results become the
+        context's frame 0 (keypoints(0), stereo(0) = all -1, undistorted_keypoints(0), searches)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        assert img.shape == (self.rows, self.cols)
+        self.cam = Camera(*cam)
+        self.check(lib().slamgpu_frame_mono(self.h, _ptr(img), img.strides[0], C.byref(self.cam)))
+
     def frontend_device(self, d_left, d_right, frame_stride, pitch, n_frames, cam, stream=None):
         """d_left/d_right: device pointers (int) or torch uint8 CUDA tensors."""
         self.cam = Camera(*cam)
@@ -476,6 +499,17 @@ class Context:
             _ptr(d_poses), _ptr(d_map_point), _ptr(d_blocked), mp_stride, _ptr(d_nmatches),
             n_frames, C.c_void_p(stream or 0)))
 
+    def search_for_initialization_device(self, d_queries, total_queries, d_q_start, d_q_count,
+                                         max_queries, d_params, d_prev_matched, d_matches12,
+                                         d_nmatches, n_frames, stream=None):
+        """slamgpu_search_for_initialization_device: INIT_QUERY records, one INIT_SEARCH record
+        per frame; d_prev_matched ([.][2] float32) and d_matches12 (int32) are parallel to
+        d_queries. Never allocates or synchronises."""
+        self.check(lib().slamgpu_search_for_initialization_device(
+            self.h, _ptr(d_queries), total_queries, _ptr(d_q_start), _ptr(d_q_count), max_queries,
+            _ptr(d_params), _ptr(d_prev_matched), _ptr(d_matches12), _ptr(d_nmatches), n_frames,
+            C.c_void_p(stream or 0)))
+
     def set_extract_fork(self, on):
         """Level 0's FAST beside the pyramid on a side stream (True, the default) or after it
         (False: a timing pass then sees each kernel alone)."""
@@ -523,6 +557,37 @@ class Context:
             self.h, frame, _ptr(queries), len(queries), _ptr(pose), _ptr(map_point),
             _ptr(blocked), len(map_point), C.byref(nm)))
         return nm.value
+
+
+    def search_for_initialization(self, frame, queries, params, prev_matched):
+        """slamgpu_search_for_initialization with F2 = frame `frame`: queries are INIT_QUERY
+        records of all F1 keypoints, params one INIT_SEARCH record, prev_matched ([n1][2] float32)
+        is updated in place. Returns (nmatches, matches12 as int32[n1])."""
+        queries = np.ascontiguousarray(queries, dtype=INIT_QUERY_DTYPE)
+        params = np.ascontiguousarray(np.atleast_1d(params), dtype=INIT_SEARCH_DTYPE)
+        assert prev_matched.dtype == np.float32 and prev_matched.flags.c_contiguous
+        assert prev_matched.shape == (len(queries), 2)
+        m12 = np.full(len(queries), -1, np.int32)
+        nm = C.c_int()
+        self.check(lib().slamgpu_search_for_initialization(
+            self.h, frame, _ptr(queries), len(queries), _ptr(params), _ptr(prev_matched),
+            _ptr(m12), C.byref(nm)))
+        return nm.value, m12
+
+
+def init_queries(keys, desc):
+    """INIT_QUERY records of a frame's undistorted keypoints (KP_DTYPE) and descriptors."""
+    q = np.zeros(len(keys), INIT_QUERY_DTYPE)
+    q["angle"] = keys["angle"]
+    q["octave"] = keys["octave"]
+    q["desc"] = np.asarray(desc, np.uint8).reshape(-1, 32)
+    return q
+
+
+def init_search(nnratio, window_size, check_ori):
+    p = np.zeros(1, INIT_SEARCH_DTYPE)
+    p["nnratio"], p["window_size"], p["check_ori"] = nnratio, window_size, 1 if check_ori else 0
+    return p
 
 
 def _io_check(rc, what):
@@ -810,6 +875,15 @@ class OrbMatcher:
         q, pose = reloc_queries(kf, already_found, Tcw, th, ORBdist, self.mbCheckOrientation)
         blocked = np.zeros(len(vpMapPoints), np.uint8)
         return ctx.search_by_projection_reloc(frame, q, pose, vpMapPoints, blocked)
+
+    def SearchForInitialization(self, ctx, frame, F1, vbPrevMatched, windowSize=10):
+        """SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
+        (orb_matcher.cpp:264-382) with F2 = frame `frame` of `ctx`'s last frame call.
+        F1: .keypoints (undistorted, KP_DTYPE) and .descriptors of the initial frame;
+        vbPrevMatched: float32 [n1][2], updated in place. Returns (nmatches, vnMatches12)."""
+        q = init_queries(F1.keypoints, F1.descriptors)
+        p = init_search(self.mfNNratio, int(windowSize), self.mbCheckOrientation)
+        return ctx.search_for_initialization(frame, q, p, vbPrevMatched)
 
     def FuseSim3(self, kf, Scw, points, th, cam, levels, grid):
         """Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (orb_matcher.cpp:956-1079): the per-point
