@@ -174,6 +174,13 @@ __device__ __forceinline__ int lane_id() { return __lane_id(); }
 __device__ __forceinline__ int wave_id() {
   return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
+// Orders the LDS and global accesses of the lanes of one wave: what any lane wrote before this
+// point, every lane of the same wave reads after it. A wavefront-scope fence and a scheduling
+// barrier the compiler moves no access across; no s_barrier, so other waves are not waited for.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
 
 // XCD-aware (image, block) of a (blocks per image, images) grid: workgroups are dealt
 // round-robin over the 8 XCDs by linear id, so give every block of one image the same

@@ -1,4 +1,6 @@
-// match_kernels.h -- device buffers and launchers of the batched matchers.
+// match_kernels.h -- device buffers and launchers of the batched frame matchers: stereo_match.hip
+// (stereo), frame_tables.hip (row table, grid, packed record, undistortion, VO queries) and
+// orb_search.hip (the OrbMatcher searches).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,6 +53,10 @@ void launch_trace_marker(int id, hipStream_t st);
 void launch_frame_pack(const FrameKps& ext, const float* u_right, const float* depth,
                        const uint32_t* err, int kp_cap, uint8_t* dst, hipStream_t st,
                        int parts = 3);
+// launch_stereo's first step, the row tables of n_frames frames (frame_tables.hip; the one call
+// between two of the matcher files)
+void launch_stereo_rows(const OrbGeomDev& g, const FrameKps& ext, int nrows, int n_frames,
+                        const StereoWorkspace& ws, hipStream_t st);
 // pack: the single-frame call's packed record (frame 0's u_right / depth go there too), or null
 void launch_stereo(const ImageBatch& b, const OrbGeomDev& g, const Camera& cam, int n_frames,
                    const StereoWorkspace& ws, const StereoOut& out, hipStream_t st,

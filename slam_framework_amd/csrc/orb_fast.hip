@@ -244,12 +244,10 @@ __global__ __launch_bounds__(64 * kCellWaves, 1) void fast_cells_kernel(ImageBat
         if (lane == 0) cell_count[slot] = 0;
         continue;
       }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       issue(v, tile0);
       __builtin_amdgcn_s_waitcnt(0x0F70);
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
     } else {
     if (v.vh == 0) {  // empty cell (:737, :745)
       if (lane == 0) cell_count[slot] = 0;
@@ -259,8 +257,7 @@ __global__ __launch_bounds__(64 * kCellWaves, 1) void fast_cells_kernel(ImageBat
       }
       continue;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();  // previous cell's LDS reads are done
+    wave_lds_sync();  // previous cell's LDS reads are done
     if (v.aligned) {
       const bool dok = pld < v.nd;
 #pragma unroll
@@ -276,8 +273,7 @@ __global__ __launch_bounds__(64 * kCellWaves, 1) void fast_cells_kernel(ImageBat
       nxt = cell_view<kAlign>(b, g, img, in_pitch, readlane4(my_desc, ci + 1));
       if (nxt.vh > 0) prefetch(nxt);
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     }
     const int off = v.off;
     const int dh = v.vh - 6, dw = v.vw - 6;  // detect area [3, vh-3) x [3, vw-3)
@@ -321,8 +317,7 @@ __global__ __launch_bounds__(64 * kCellWaves, 1) void fast_cells_kernel(ImageBat
       int it = 0, r0 = 0;
       for (; r0 + rows_per <= dh; r0 += rows_per, it++) step(it, r0, std::false_type{});
       if (r0 < dh) step(it, r0, std::true_type{});
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       // records -> one candidate per surviving pixel, row-major (exclusive prefix of the
       // per-record counts via 3 ballots)
       int ncand = 0;
@@ -342,20 +337,17 @@ __global__ __launch_bounds__(64 * kCellWaves, 1) void fast_cells_kernel(ImageBat
           if (fl & (0x80u << (8 * bb))) cand[pos++] = (uint16_t)(pix0 + bb);
         ncand += __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
       }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       // the map is zero but for the records just read (it is zeroed once per wave and every
       // pass clears what it wrote): clear them
       for (int i = lane; i < nrec; i += 64) recs[i] = 0u;
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       // exact FAST score of the survivors (window top-left: tile (r, cc - 3) = tile + pix - 3)
       for (int i = lane; i < ncand; i += 64) {
         const int pix = cand[i];
         sc1[pix] = (uint8_t)fast_score<TS>(tile + pix - 3);
       }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       // NMS at th: cv::FAST keeps p iff s - 1 > ns for all 8 neighbours, ns = (q > th ? q - 1 :
       // 0), zero outside the detect area. With Q = max of the 8 neighbours' s that is
       //   s > th  &&  s >= 2  &&  Q < max(s, th + 1),
@@ -391,8 +383,7 @@ __global__ __launch_bounds__(64 * kCellWaves, 1) void fast_cells_kernel(ImageBat
         }
         count += __popcll(mk);
       }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       for (int i = lane; i < ncand; i += 64) sc1[cand[i]] = 0;  // the map back to zero
       return count;
     };
@@ -400,8 +391,7 @@ __global__ __launch_bounds__(64 * kCellWaves, 1) void fast_cells_kernel(ImageBat
     // NMS) is empty (:753-757)
     int count = fast_pass(th_ini);
     if (count == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       count = fast_pass(th_min);
     }
     if (count > cell_cap) {

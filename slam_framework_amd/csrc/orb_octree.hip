@@ -776,8 +776,7 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
         carry += ctot;
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     const int R = (K + 63) >> 6;
     const int ng = (ncell + kCellGroup - 1) / kCellGroup;  // <= kMaxGroups
     uint32_t kr[kGatherRegs];
@@ -909,8 +908,7 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
       }
       for (int k = 2; k <= P2; k <<= 1)
         for (int jj = k >> 1; jj > 0; jj >>= 1) {
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-          __builtin_amdgcn_wave_barrier();
+          wave_lds_sync();
           for (int i = lane; i < P2; i += 64) {
             const int ixj = i ^ jj;
             if (ixj > i) {
@@ -923,8 +921,7 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
             }
           }
         }
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
     }
     auto nidx = [&](int j) { return outer ? j : 4095 - (int)(sortk[j] & 0xfffu); };
     // -- count children: t (non-empty), e (> 1 key); pu = survivor flag (outer) or t - 1
@@ -983,15 +980,12 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
         carry += tot;
       }
       for (int i = lane; i < m; i += 64) processed[i] = 0;
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       for (int j = lane; j < nproc; j += 64) processed[nidx(j)] = 1;
-      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      wave_lds_sync();
       for (int i = lane; i < m; i += 64) pu[i] = (int16_t)(processed[i] ? 0 : 1);
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     const int T = wave_scan_array(pt, nproc, lane);  // push-order child positions
     const int E = wave_scan_array(pe, nproc, lane);
     const int U = wave_scan_array(pu, m, lane);      // survivors keep their order
@@ -1000,8 +994,7 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
       if (lane == 0) atomicOr(err, kErrNodeOverflow);
       break;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     // -- divide in place and place children: push order gpos -> list position T-1-gpos
     auto place = [&](int j, const OctNodeS& nd, uint32_t c4) {
       int gpos = pt[j], epos = pe[j];
@@ -1071,8 +1064,7 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
       const OctNodeS nd = Lc[i];
       if (outer ? node_n(nd) == 1 : !processed[i]) Ln[T + pu[i]] = nd;
     }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     for (int i = lane; i < E; i += 64) sortk[i] = (uint32_t)vnext[i];
     const int mprev = m;
     m = newm;
@@ -1082,8 +1074,7 @@ __global__ __launch_bounds__(64 * kMaxLevels) void octree_img_kernel(
     if (outer && newm + E * 3 > N) outer = false;
   }
   // ---- 4. retain the best key of each node (:682-701): strict '>' keeps the first maximum
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+  wave_lds_sync();
   const OctNodeS* Lf = lists + cur * NC;
   const int mout = min(m, L.out_cap);
   for (int j = lane; j < mout; j += 64) {

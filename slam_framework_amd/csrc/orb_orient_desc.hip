@@ -553,8 +553,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void o
     // the window has landed (buffer-to-LDS loads count in vmcnt; border windows were stored by
     // this wave's own ds_writes, which its LDS reads follow in order): the A operands
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
     u32x4 axn[3];
 #pragma unroll
     for (int ti = 0; ti < 3; ti++) axn[ti] = *reinterpret_cast<const u32x4*>(win + a_lds[ti]);

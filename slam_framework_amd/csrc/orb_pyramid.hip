@@ -126,8 +126,7 @@ __device__ __forceinline__ void pyr_strip(const ImageBatch& b, const OrbGeom* __
           (uint32_t)((sy_lo + r) * spitch + seg0 + 16 * cl), 0, 0, 0);
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the rows have landed
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_sync();
   }
   auto fetch = [&](int sy, uint32_t (&wv)[3]) {
     const int roff = __builtin_amdgcn_readfirstlane((min(sy, sy_hi) - srow0) * spitch);

@@ -1,5 +1,5 @@
 // orbmatch_device.h -- the rules of OrbMatcher (src/orb_features/orb_matcher.cpp) that every
-// matcher kernel restates, once: match_kernels.hip (frame matchers), kfmatch.hip (LocalMapper),
+// matcher kernel restates, once: orb_search.hip (frame matchers), kfmatch.hip (LocalMapper),
 // loopmatch.hip (LoopCloser) and bow_kernels.hip (SearchByBoW) all call these. Device code only
 // (no host staging). Every expression keeps the reference's order, width and fmaf placement (the
 // library builds with -ffp-contract=off; results are compared bit for bit with the oracles).

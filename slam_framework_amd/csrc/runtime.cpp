@@ -13,7 +13,10 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/slamgpu.h"
@@ -22,6 +25,7 @@
 #include "undistort.h"
 #include "orb_kernels.h"
 #include "orb_tables.h"
+#include "stage_layout.h"
 #include "timing.h"
 
 using namespace slamgpu;
@@ -971,6 +975,28 @@ int slamgpu_descriptor_distance(const uint8_t* a, const uint8_t* b) {
 
 // ---- matchers ------------------------------------------------------------------------------
 
+// The arguments of the four *_device searches and their per-query workspace. `always`: pointers
+// every call reads or writes; `with_queries`: those touched only if a frame can have a query. A
+// search without map point slots passes kp_cap as mp_stride. Frame-to-frame and local map may
+// grow the workspace; relocalisation and initialisation never allocate: it holds max_frames *
+// kp_cap queries from creation on (a keyframe's slots, a frame's keypoints) or more.
+static int check_search_args(slamgpu_ctx* c, const char* name, int total_queries, int max_queries,
+                             int n_frames, int64_t mp_stride, bool may_grow,
+                             std::initializer_list<const void*> always,
+                             std::initializer_list<const void*> with_queries) {
+  if (!c) return SLAMGPU_EINVAL;
+  bool ok = c->have_cam && n_frames >= 1 && n_frames <= c->n_frames_last &&
+            mp_stride >= c->geom.kp_cap && total_queries >= 0 && max_queries >= 0;
+  for (const void* p : always) ok = ok && p;
+  for (const void* p : with_queries) ok = ok && (p || max_queries == 0);
+  if (!ok) return slot(c).fail(SLAMGPU_EINVAL, "%s: bad arguments", name);
+  if (may_grow) return ensure_match_ws(c, total_queries);
+  if (total_queries > c->mw_cap)
+    return slot(c).fail(SLAMGPU_ECAP, "%s: %d queries, the workspace holds %d", name,
+                        total_queries, c->mw_cap);
+  return 0;
+}
+
 int slamgpu_search_by_projection_frame_device(slamgpu_ctx* c, const slamgpu_f2f_query* d_q,
                                               int total_queries, const int* d_q_start,
                                               const int* d_q_count, int max_queries,
@@ -978,11 +1004,10 @@ int slamgpu_search_by_projection_frame_device(slamgpu_ctx* c, const slamgpu_f2f_
                                               int32_t* d_map_point, uint8_t* d_blocked,
                                               int64_t mp_stride, int* d_nmatches, int n_frames,
                                               void* stream) {
-  if (!c || !c->have_cam || n_frames < 1 || n_frames > c->n_frames_last ||
-      mp_stride < c->geom.kp_cap)
-    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_frame_device: bad arguments");
-  int rc = ensure_match_ws(c, total_queries);
-  if (rc) return rc;
+  if (int rc = check_search_args(
+          c, "search_by_projection_frame_device", total_queries, max_queries, n_frames, mp_stride,
+          true, {d_q_start, d_q_count, d_poses, d_map_point, d_blocked, d_nmatches}, {d_q}))
+    return rc;
   MatchIO io{d_q_start, d_q_count, d_map_point, d_blocked, d_nmatches, mp_stride};
   TimerScope ts(c);
   launch_search_frame(left_views(c), c->sout.u_right, c->geom.kp_cap, c->cam, c->gd(),
@@ -999,11 +1024,10 @@ int slamgpu_search_by_projection_mps_device(slamgpu_ctx* c, const slamgpu_mps_qu
                                             int th, int32_t* d_map_point, uint8_t* d_blocked,
                                             int64_t mp_stride, int* d_nmatches, int n_frames,
                                             void* stream) {
-  if (!c || !c->have_cam || n_frames < 1 || n_frames > c->n_frames_last ||
-      mp_stride < c->geom.kp_cap)
-    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_mps_device: bad arguments");
-  int rc = ensure_match_ws(c, total_queries);
-  if (rc) return rc;
+  if (int rc = check_search_args(
+          c, "search_by_projection_mps_device", total_queries, max_queries, n_frames, mp_stride,
+          true, {d_q_start, d_q_count, d_map_point, d_blocked, d_nmatches}, {d_q}))
+    return rc;
   MatchIO io{d_q_start, d_q_count, d_map_point, d_blocked, d_nmatches, mp_stride};
   TimerScope ts(c);
   launch_search_mps(left_views(c), c->sout.u_right, c->geom.kp_cap, c->cam, c->gd(),
@@ -1020,17 +1044,10 @@ int slamgpu_search_by_projection_reloc_device(slamgpu_ctx* c, const slamgpu_relo
                                               int32_t* d_map_point, uint8_t* d_blocked,
                                               int64_t mp_stride, int* d_nmatches, int n_frames,
                                               void* stream) {
-  if (!c) return SLAMGPU_EINVAL;
-  if (!c->have_cam || n_frames < 1 || n_frames > c->n_frames_last || mp_stride < c->geom.kp_cap ||
-      total_queries < 0 || max_queries < 0 || (max_queries > 0 && !d_q) || !d_q_start ||
-      !d_q_count || !d_poses || !d_map_point || !d_blocked || !d_nmatches)
-    return slot(c).fail(SLAMGPU_EINVAL, "search_by_projection_reloc_device: bad arguments");
-  // never allocates: the workspace holds max_frames * kp_cap queries from creation on (a
-  // keyframe has at most kp_cap map point slots); the synchronous calls may have grown it
-  if (total_queries > c->mw_cap)
-    return slot(c).fail(SLAMGPU_ECAP,
-                        "search_by_projection_reloc_device: %d queries, the workspace holds %d",
-                        total_queries, c->mw_cap);
+  if (int rc = check_search_args(
+          c, "search_by_projection_reloc_device", total_queries, max_queries, n_frames, mp_stride,
+          false, {d_q_start, d_q_count, d_poses, d_map_point, d_blocked, d_nmatches}, {d_q}))
+    return rc;
   MatchIO io{d_q_start, d_q_count, d_map_point, d_blocked, d_nmatches, mp_stride};
   TimerScope ts(c);
   launch_search_reloc(left_views(c), c->sout.u_right, c->geom.kp_cap, c->cam, c->gd(),
@@ -1047,16 +1064,11 @@ int slamgpu_search_for_initialization_device(slamgpu_ctx* c, const slamgpu_init_
                                              const slamgpu_init_search* d_params,
                                              float* d_prev_matched, int32_t* d_matches12,
                                              int* d_nmatches, int n_frames, void* stream) {
-  if (!c) return SLAMGPU_EINVAL;
-  if (!c->have_cam || n_frames < 1 || n_frames > c->n_frames_last || total_queries < 0 ||
-      max_queries < 0 || (max_queries > 0 && (!d_q || !d_prev_matched || !d_matches12)) ||
-      !d_q_start || !d_q_count || !d_params || !d_nmatches)
-    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization_device: bad arguments");
-  // never allocates: the workspace holds max_frames * kp_cap queries from creation on
-  if (total_queries > c->mw_cap)
-    return slot(c).fail(SLAMGPU_ECAP,
-                        "search_for_initialization_device: %d queries, the workspace holds %d",
-                        total_queries, c->mw_cap);
+  if (int rc = check_search_args(c, "search_for_initialization_device", total_queries,
+                                 max_queries, n_frames, c ? c->geom.kp_cap : 0, false,
+                                 {d_q_start, d_q_count, d_params, d_nmatches},
+                                 {d_q, d_prev_matched, d_matches12}))
+    return rc;
   InitIO io{d_q_start, d_q_count, d_prev_matched, d_matches12, d_nmatches};
   TimerScope ts(c);
   launch_search_init(left_views(c), c->cam, c->gd(), reinterpret_cast<const InitQuery*>(d_q),
@@ -1066,137 +1078,94 @@ int slamgpu_search_for_initialization_device(slamgpu_ctx* c, const slamgpu_init_
   return 0;
 }
 
-// The host form: F1's queries, the parameters, vbPrevMatched and vnMatches12 staged in the
-// query buffer host_search uses, one frame's view, one synchronisation.
-int slamgpu_search_for_initialization(slamgpu_ctx* c, int frame, const slamgpu_init_query* q,
-                                      int n1, const slamgpu_init_search* params,
-                                      float* prev_matched, int32_t* matches12, int* nmatches) {
-  if (!c) return SLAMGPU_EINVAL;
-  if (!params || !nmatches || n1 < 0 || (n1 > 0 && (!q || !prev_matched || !matches12)))
-    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: null argument or n1 < 0");
-  if (!c->have_cam || frame < 0 || frame >= c->n_frames_last)
-    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: frame %d outside [0, %d)",
-                        frame, c->n_frames_last);
-  if (params->window_size < 0)
-    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: window_size %d < 0",
-                        params->window_size);
-  if (!std::isfinite(params->nnratio))
-    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: nnratio is not finite");
-  HIPCHECK(c->err, hipSetDevice(c->device));
-  const size_t nq = (size_t)std::max(n1, 1);
-  const size_t off_p = (sizeof(InitQuery) * nq + 255) / 256 * 256;
-  const size_t off_prev = off_p + 256, off_m = off_prev + (8 * nq + 255) / 256 * 256;
-  const size_t need = off_m + 4 * nq + 256;
-  if (need > c->qbuf_bytes) {
-    if (int rc = dalloc(c, reinterpret_cast<uint8_t**>(&c->d_qbuf), need)) return rc;
-    c->qbuf_bytes = need;
-  }
-  if (int rc = ensure_match_ws(c, n1)) return rc;
-  hipStream_t st = c->stream;
-  uint8_t* qb = static_cast<uint8_t*>(c->d_qbuf);
-  float* d_prev = reinterpret_cast<float*>(qb + off_prev);
-  int32_t* d_m12 = reinterpret_cast<int32_t*>(qb + off_m);
-  if (n1) {
-    HIPCHECK(c->err, hipMemcpyAsync(qb, q, sizeof(InitQuery) * n1, hipMemcpyHostToDevice, st));
-    HIPCHECK(c->err, hipMemcpyAsync(d_prev, prev_matched, 8 * (size_t)n1, hipMemcpyHostToDevice, st));
-  }
-  HIPCHECK(c->err, hipMemcpyAsync(qb + off_p, params, sizeof(InitSearch), hipMemcpyHostToDevice, st));
-  int meta[2] = {0, n1};
-  HIPCHECK(c->err, hipMemcpyAsync(c->d_qmeta, meta, sizeof(meta), hipMemcpyHostToDevice, st));
+}  // extern "C"
+
+// Host-buffer matcher calls on one frame of the last frontend / frame call: the launchers get a
+// one-frame view shifted to that frame -- its left keypoints and its grid.
+struct FrameSlice { FrameKps cur; GridWorkspace gw; };
+static FrameSlice frame_slice(const slamgpu_ctx* c, int frame) {
   const int64_t kc = c->geom.kp_cap;
-  FrameKps cur{(c->dist_on ? c->kps_un : c->out.kps) + 2 * frame * kc,
-               c->out.desc + 2 * frame * kc * 32, c->out.nkps + 2 * frame, 2 * kc, 2};
-  GridWorkspace gw = c->gws;
-  gw.cell_start += (int64_t)frame * (kGridCells + 1);
-  gw.cell_items += (int64_t)frame * kc;
-  InitIO io{c->d_qmeta, c->d_qmeta + 1, d_prev, d_m12, c->d_nm};
-  {
-    TimerScope ts(c);
-    launch_search_init(cur, c->cam, c->gd(), reinterpret_cast<const InitQuery*>(qb),
-                       reinterpret_cast<const InitSearch*>(qb + off_p), 1, n1, gw, c->mws, io, st);
-  }
-  HIPCHECK(c->err, hipGetLastError());
-  // staged on the host side first: nothing is written unless the whole call succeeds
-  std::vector<float> h_prev(2 * (size_t)n1);
-  std::vector<int32_t> h_m12((size_t)n1);
-  if (n1) {
-    HIPCHECK(c->err, hipMemcpyAsync(h_prev.data(), d_prev, 8 * (size_t)n1, hipMemcpyDeviceToHost, st));
-    HIPCHECK(c->err, hipMemcpyAsync(h_m12.data(), d_m12, 4 * (size_t)n1, hipMemcpyDeviceToHost, st));
-  }
-  int nm = 0;
-  HIPCHECK(c->err, hipMemcpyAsync(&nm, c->d_nm, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHECK(c->err, hipStreamSynchronize(st));
-  if (int rc = check_device_err(c)) return rc;
-  if (n1) {
-    std::memcpy(prev_matched, h_prev.data(), 8 * (size_t)n1);
-    std::memcpy(matches12, h_m12.data(), 4 * (size_t)n1);
-  }
-  *nmatches = nm;
+  FrameSlice s{{(c->dist_on ? c->kps_un : c->out.kps) + 2 * frame * kc,
+                c->out.desc + 2 * frame * kc * 32, c->out.nkps + 2 * frame, 2 * kc, 2}, c->gws};
+  s.gw.cell_start += (int64_t)frame * (kGridCells + 1);
+  s.gw.cell_items += (int64_t)frame * kc;
+  return s;
+}
+
+// The query buffer they stage in (by stage_layout.h's layouts), grown on demand.
+static int reserve_qbuf(slamgpu_ctx* c, size_t bytes) {
+  if (bytes <= c->qbuf_bytes) return 0;
+  if (int rc = dalloc(c, reinterpret_cast<uint8_t**>(&c->d_qbuf), bytes)) return rc;
+  c->qbuf_bytes = bytes;
   return 0;
 }
 
-}  // extern "C"
+struct StageCopy { void* dst; const void* src; size_t bytes; };  // bytes == 0: no copy
+static int copy_all(slamgpu_ctx* c, std::initializer_list<StageCopy> arrays, hipMemcpyKind kind) {
+  for (const StageCopy& a : arrays)
+    if (a.bytes) HIPCHECK(c->err, hipMemcpyAsync(a.dst, a.src, a.bytes, kind, c->stream));
+  return 0;
+}
 
-// Host-buffer matcher calls on one frame of the last frontend/frame call.
-enum { kSearchF2F, kSearchMps, kSearchReloc };
+// What every host call does on the context's stream: `up` and the query range [0, nq) go to the
+// device, `launch` runs on the frame's slice (after staging of its own, if any), `down` and the
+// match count come back, one synchronisation. The device error word is the caller's to check.
+template <typename Launch>
+static int run_host_search(slamgpu_ctx* c, int frame, int nq, std::initializer_list<StageCopy> up,
+                           Launch launch, std::initializer_list<StageCopy> down, int* nm) {
+  hipStream_t st = c->stream;
+  if (int rc = copy_all(c, up, hipMemcpyHostToDevice)) return rc;
+  const int meta[2] = {0, nq};
+  HIPCHECK(c->err, hipMemcpyAsync(c->d_qmeta, meta, sizeof(meta), hipMemcpyHostToDevice, st));
+  if (int rc = launch(frame_slice(c, frame), st)) return rc;
+  HIPCHECK(c->err, hipGetLastError());
+  if (int rc = copy_all(c, down, hipMemcpyDeviceToHost)) return rc;
+  HIPCHECK(c->err, hipMemcpyAsync(nm, c->d_nm, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHECK(c->err, hipStreamSynchronize(st));
+  return 0;
+}
+
+// The three SearchByProjection overloads: queries and pose (`extra`) up, slot arrays up and back.
 template <typename QT>
 static int host_search(slamgpu_ctx* c, int frame, const QT* queries, int nq, int32_t* map_point,
                        uint8_t* blocked, int n, int* nmatches, size_t extra_bytes,
-                       const void* extra, int kind, float nnratio, int th) {
+                       const void* extra, float nnratio = 0.f, int th = 0) {
   if (!c || frame < 0 || frame >= c->n_frames_last || nq < 0 || !map_point || !blocked)
     return SLAMGPU_EINVAL;
   if (n > c->geom.kp_cap) return slot(c).fail(SLAMGPU_EINVAL, "n > kp capacity");
-  const size_t need = sizeof(QT) * (size_t)std::max(nq, 1) + extra_bytes + 256;
-  if (need > c->qbuf_bytes) {
-    int rc = dalloc(c, reinterpret_cast<uint8_t**>(&c->d_qbuf), need);
-    if (rc) return rc;
-    c->qbuf_bytes = need;
-  }
-  int rc = ensure_match_ws(c, nq);
-  if (rc) return rc;
-  hipStream_t st = c->stream;
-  uint8_t* qb = static_cast<uint8_t*>(c->d_qbuf);
-  if (nq) HIPCHECK(c->err, hipMemcpyAsync(qb, queries, sizeof(QT) * nq, hipMemcpyHostToDevice, st));
-  uint8_t* eb = qb + (sizeof(QT) * (size_t)std::max(nq, 1) + 255) / 256 * 256;
-  if (extra_bytes)
-    HIPCHECK(c->err, hipMemcpyAsync(eb, extra, extra_bytes, hipMemcpyHostToDevice, st));
-  // frame `frame` only: use a one-frame view shifted to that frame
-  int meta[2] = {0, nq};
-  HIPCHECK(c->err, hipMemcpyAsync(c->d_qmeta, meta, sizeof(meta), hipMemcpyHostToDevice, st));
-  HIPCHECK(c->err, hipMemsetAsync(c->d_mp, 0xff, sizeof(int32_t) * c->geom.kp_cap, st));
-  HIPCHECK(c->err, hipMemsetAsync(c->d_blk, 0, c->geom.kp_cap, st));
-  if (n) {
-    HIPCHECK(c->err, hipMemcpyAsync(c->d_mp, map_point, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
-    HIPCHECK(c->err, hipMemcpyAsync(c->d_blk, blocked, n, hipMemcpyHostToDevice, st));
-  }
+  StageLayout L;
+  const FrameSearchLayout at = layout_frame_search(L, nq, sizeof(QT), extra_bytes);
+  if (int rc = reserve_qbuf(c, L.size())) return rc;
+  if (int rc = ensure_match_ws(c, nq)) return rc;
+  uint8_t* qb = static_cast<uint8_t*>(c->d_qbuf) + at.queries;
+  uint8_t* eb = static_cast<uint8_t*>(c->d_qbuf) + at.extra;
   const int64_t kc = c->geom.kp_cap;
-  FrameKps cur{(c->dist_on ? c->kps_un : c->out.kps) + 2 * frame * kc,
-               c->out.desc + 2 * frame * kc * 32, c->out.nkps + 2 * frame, 2 * kc, 2};
-  GridWorkspace gw = c->gws;
-  gw.cell_start += (int64_t)frame * (kGridCells + 1);
-  gw.cell_items += (int64_t)frame * kc;
-  MatchIO io{c->d_qmeta, c->d_qmeta + 1, c->d_mp, c->d_blk, c->d_nm, kc};
-  TimerScope ts(c);
-  if (kind == kSearchF2F)
-    launch_search_frame(cur, c->sout.u_right + frame * kc, kc, c->cam, c->gd(),
-                        reinterpret_cast<const F2FQuery*>(qb),
-                        reinterpret_cast<const F2FPose*>(eb), 1, nq, gw, c->mws, io, st);
-  else if (kind == kSearchReloc)
-    launch_search_reloc(cur, c->sout.u_right + frame * kc, kc, c->cam, c->gd(),
-                        reinterpret_cast<const RelocQuery*>(qb),
-                        reinterpret_cast<const RelocPose*>(eb), 1, nq, gw, c->mws, io, st);
-  else
-    launch_search_mps(cur, c->sout.u_right + frame * kc, kc, c->cam, c->gd(),
-                      reinterpret_cast<const MpsQuery*>(qb), nnratio, th, 1, nq, gw, c->mws, io,
-                      st);
-  HIPCHECK(c->err, hipGetLastError());
-  if (n) {
-    HIPCHECK(c->err, hipMemcpyAsync(map_point, c->d_mp, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-    HIPCHECK(c->err, hipMemcpyAsync(blocked, c->d_blk, n, hipMemcpyDeviceToHost, st));
-  }
+  const size_t mp_bytes = sizeof(int32_t) * n, blk_bytes = n;
+  auto launch = [&](const FrameSlice& s, hipStream_t st) {
+    HIPCHECK(c->err, hipMemsetAsync(c->d_mp, 0xff, sizeof(int32_t) * kc, st));
+    HIPCHECK(c->err, hipMemsetAsync(c->d_blk, 0, kc, st));
+    if (int rc = copy_all(c, {{c->d_mp, map_point, mp_bytes}, {c->d_blk, blocked, blk_bytes}},
+                          hipMemcpyHostToDevice))
+      return rc;
+    const float* ur = c->sout.u_right + frame * kc;
+    MatchIO io{c->d_qmeta, c->d_qmeta + 1, c->d_mp, c->d_blk, c->d_nm, kc};
+    TimerScope ts(c);
+    if constexpr (std::is_same<QT, slamgpu_f2f_query>::value)
+      launch_search_frame(s.cur, ur, kc, c->cam, c->gd(), reinterpret_cast<const F2FQuery*>(qb),
+                          reinterpret_cast<const F2FPose*>(eb), 1, nq, s.gw, c->mws, io, st);
+    else if constexpr (std::is_same<QT, slamgpu_reloc_query>::value)
+      launch_search_reloc(s.cur, ur, kc, c->cam, c->gd(), reinterpret_cast<const RelocQuery*>(qb),
+                          reinterpret_cast<const RelocPose*>(eb), 1, nq, s.gw, c->mws, io, st);
+    else
+      launch_search_mps(s.cur, ur, kc, c->cam, c->gd(), reinterpret_cast<const MpsQuery*>(qb),
+                        nnratio, th, 1, nq, s.gw, c->mws, io, st);
+    return 0;
+  };
   int nm = 0;
-  HIPCHECK(c->err, hipMemcpyAsync(&nm, c->d_nm, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIPCHECK(c->err, hipStreamSynchronize(st));
+  if (int rc = run_host_search(
+          c, frame, nq, {{qb, queries, sizeof(QT) * nq}, {eb, extra, extra_bytes}}, launch,
+          {{map_point, c->d_mp, mp_bytes}, {blocked, c->d_blk, blk_bytes}}, &nm))
+    return rc;
   if (nmatches) *nmatches = nm;
   return check_device_err(c);
 }
@@ -1207,15 +1176,13 @@ int slamgpu_search_by_projection_frame(slamgpu_ctx* c, int frame, const slamgpu_
                                        int nq, const slamgpu_f2f_pose* pose, int32_t* map_point,
                                        uint8_t* blocked, int n, int* nmatches) {
   if (!pose) return SLAMGPU_EINVAL;
-  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, sizeof(slamgpu_f2f_pose),
-                     pose, kSearchF2F, 0.f, 0);
+  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, sizeof(*pose), pose);
 }
 
 int slamgpu_search_by_projection_mps(slamgpu_ctx* c, int frame, const slamgpu_mps_query* q,
                                      int nq, float nnratio, int th, int32_t* map_point,
                                      uint8_t* blocked, int n, int* nmatches) {
-  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, 0, nullptr, kSearchMps,
-                     nnratio, th);
+  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, 0, nullptr, nnratio, th);
 }
 
 int slamgpu_search_by_projection_reloc(slamgpu_ctx* c, int frame, const slamgpu_reloc_query* q,
@@ -1239,8 +1206,59 @@ int slamgpu_search_by_projection_reloc(slamgpu_ctx* c, int frame, const slamgpu_
                         "keypoints", n, nk);
   // blocked = "the slot holds a map point" (CurrentFrame.GetMapPoint(i2) != nullptr, :1526)
   for (int i = 0; i < n; i++) blocked[i] = map_point[i] >= 0;
-  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, sizeof(slamgpu_reloc_pose),
-                     pose, kSearchReloc, 0.f, 0);
+  return host_search(c, frame, q, nq, map_point, blocked, n, nmatches, sizeof(*pose), pose);
+}
+
+// F1's queries, the parameters and vbPrevMatched up, vbPrevMatched and vnMatches12 back -- into
+// host staging first: nothing is written unless the whole call succeeds.
+int slamgpu_search_for_initialization(slamgpu_ctx* c, int frame, const slamgpu_init_query* q,
+                                      int n1, const slamgpu_init_search* params,
+                                      float* prev_matched, int32_t* matches12, int* nmatches) {
+  if (!c) return SLAMGPU_EINVAL;
+  if (!params || !nmatches || n1 < 0 || (n1 > 0 && (!q || !prev_matched || !matches12)))
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: null argument or n1 < 0");
+  if (!c->have_cam || frame < 0 || frame >= c->n_frames_last)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: frame %d outside [0, %d)",
+                        frame, c->n_frames_last);
+  if (params->window_size < 0)
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: window_size %d < 0",
+                        params->window_size);
+  if (!std::isfinite(params->nnratio))
+    return slot(c).fail(SLAMGPU_EINVAL, "search_for_initialization: nnratio is not finite");
+  HIPCHECK(c->err, hipSetDevice(c->device));
+  StageLayout L;
+  const InitSearchLayout at = layout_init_search(L, n1);
+  if (int rc = reserve_qbuf(c, L.size())) return rc;
+  if (int rc = ensure_match_ws(c, n1)) return rc;
+  uint8_t* qb = static_cast<uint8_t*>(c->d_qbuf);
+  float* d_prev = reinterpret_cast<float*>(qb + at.prev_matched);
+  int32_t* d_m12 = reinterpret_cast<int32_t*>(qb + at.matches12);
+  const size_t prev_bytes = 8 * (size_t)n1, m12_bytes = 4 * (size_t)n1;
+  const std::unique_ptr<uint8_t[]> h(new uint8_t[prev_bytes + m12_bytes]);  // not zeroed
+  uint8_t *h_prev = h.get(), *h_m12 = h_prev + prev_bytes;
+  auto launch = [&](const FrameSlice& s, hipStream_t st) {
+    InitIO io{c->d_qmeta, c->d_qmeta + 1, d_prev, d_m12, c->d_nm};
+    TimerScope ts(c);
+    launch_search_init(s.cur, c->cam, c->gd(), reinterpret_cast<const InitQuery*>(qb + at.queries),
+                       reinterpret_cast<const InitSearch*>(qb + at.params), 1, n1, s.gw, c->mws,
+                       io, st);
+    return 0;
+  };
+  int nm = 0;
+  if (int rc = run_host_search(c, frame, n1,
+                               {{qb + at.queries, q, sizeof(InitQuery) * n1},
+                                {d_prev, prev_matched, prev_bytes},
+                                {qb + at.params, params, sizeof(InitSearch)}},
+                               launch, {{h_prev, d_prev, prev_bytes}, {h_m12, d_m12, m12_bytes}},
+                               &nm))
+    return rc;
+  if (int rc = check_device_err(c)) return rc;
+  if (n1) {
+    std::memcpy(prev_matched, h_prev, prev_bytes);
+    std::memcpy(matches12, h_m12, m12_bytes);
+  }
+  *nmatches = nm;
+  return 0;
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/slamgpu.h"
 #include "../../include/slamgpu_bow.h"
 #include "../../include/slamgpu_initializer.h"
 #include "../../include/slamgpu_loopmatch.h"
@@ -185,6 +186,23 @@ inline InitRansacLayout layout_init_ransac(StageLayout& L, size_t n1, size_t n2,
           L.take<slamgpu_init_motion>(SLAMGPU_INIT_MAX_MOTIONS),
           L.take<uint64_t>(SLAMGPU_INIT_MAX_MOTIONS * words),
           L.take<float>(SLAMGPU_INIT_MAX_MOTIONS * 3 * n1)};
+}
+
+// The synchronous SearchByProjection calls of one frame (frame-to-frame, local map,
+// relocalisation): nq queries of query_bytes each, then the pose record (extra_bytes; the
+// local-map search has none).
+struct FrameSearchLayout { size_t queries, extra; };
+inline FrameSearchLayout layout_frame_search(StageLayout& L, size_t nq, size_t query_bytes,
+                                             size_t extra_bytes) {
+  return {L.take(nq * query_bytes), L.take(extra_bytes)};
+}
+
+// The synchronous SearchForInitialization of one frame: n1 queries, the parameters, and the
+// arrays parallel to the queries (vbPrevMatched in and out, vnMatches12 out).
+struct InitSearchLayout { size_t queries, params, prev_matched, matches12; };
+inline InitSearchLayout layout_init_search(StageLayout& L, size_t n1) {
+  return {L.take<slamgpu_init_query>(n1), L.take<slamgpu_init_search>(1), L.take<float>(2 * n1),
+          L.take<int32_t>(n1)};
 }
 
 // A host FeatureVector (n_nodes > 0) must be well formed before its indices reach the device:

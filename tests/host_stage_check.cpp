@@ -152,6 +152,29 @@ static void walk_layouts() {
              "%s: strided arrays", what);
     }
   }
+  // the frame matchers' query buffer: the three SearchByProjection calls (64- and 80-byte queries,
+  // a 72-byte pose record or none) and SearchForInitialization
+  for (int nq : {0, 1, 3, 4097}) {
+    for (size_t query_bytes : {sizeof(slamgpu_f2f_query), sizeof(slamgpu_mps_query)})
+      for (size_t extra : {(size_t)0, (size_t)72}) {
+        Walk w;
+        const FrameSearchLayout s = layout_frame_search(w.L, nq, query_bytes, extra);
+        std::snprintf(what, sizeof(what), "frame_search nq=%d query_bytes=%zu extra_bytes=%zu", nq,
+                      query_bytes, extra);
+        w.check(what, 2);
+        EXPECT(s.queries == 0 && s.extra == w.at(1), "%s: fields", what);
+        EXPECT(s.extra >= (size_t)nq * query_bytes && s.extra + extra <= w.L.size(),
+               "%s: pose record at %zu", what, s.extra);
+      }
+    Walk w;
+    const InitSearchLayout s = layout_init_search(w.L, nq);
+    std::snprintf(what, sizeof(what), "init_search n1=%d", nq);
+    w.check(what, 4);
+    EXPECT(s.queries == 0 && s.params == w.at(1) && s.prev_matched == w.at(2) &&
+               s.matches12 == w.at(3), "%s: fields", what);
+    EXPECT(s.matches12 - s.prev_matched >= 8 * (size_t)nq &&
+               s.matches12 + 4 * (size_t)nq <= w.L.size(), "%s: per-query arrays", what);
+  }
   // local / global BA: the I/O block is one contiguous region [0, io), the workspace starts at io
   const int small[] = {0, 1, 7};
   for (int n_kf : small)

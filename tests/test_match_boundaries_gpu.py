@@ -1,5 +1,5 @@
 """The constructed boundary cases of tests/boundary_scenario.py on the device matchers
-(kfmatch.hip, loopmatch.hip, the search_cand / search_resolve kernels of match_kernels.hip): the
+(kfmatch.hip, loopmatch.hip, the search_cand / search_resolve kernels of orb_search.hip): the
 device call's whole output arrays and counts equal the CPU restatement's, which
 tests/test_match_boundaries.py holds to the expectations written down from orb_matcher.cpp. Every
 case runs through the single call of its entry point, and once through the batched device form of

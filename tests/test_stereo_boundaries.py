@@ -9,7 +9,7 @@ tolerances: every comparison is of bytes.
 The reference's branches that no input reaches get no case but an assertion over every trace:
   maxU < 0 (:459) and iniu < 0 || endu >= cols (:513): keypoints lie at least 19 level pixels
       inside every level and maxU = uL >= 19; the window reaches 10 pixels from the keypoint.
-  the kernel's extra ROI guard (match_kernels.hip, the line after endu): the same margin.
+  the kernel's extra ROI guard (stereo_match.hip, the line after endu): the same margin.
   deltaR < -1 || deltaR > 1 (:544): dist2 is the strict first minimum and the offsets beside
       it exist, so the denominator 2 ((d1 - d2) + (d3 - d2)) is positive and |d1 - d3| is at most
       half of it: |deltaR| <= 0.5, never NaN."""
