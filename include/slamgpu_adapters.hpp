@@ -741,6 +741,183 @@ inline std::vector<std::pair<int, int>> search_for_triangulation(
   return pairs;
 }
 
+// ---- LocalMapper::ComputeFundamentalMatrix (local_mapper.cpp:615-630) under the cv::Mat rules
+// of DESIGN.md "CreateNewMapPoints": a product is a double sum over ascending k rounded to float
+// once, a chain runs left to right as written (R12 = R1w * R2w.t(); t12 = ((-R1w) * R2w.t()) *
+// t2w + t1w; F12 = ((K1.t().inv() * t12x) * R12) * K2.inv()), inv() of a 3 x 3 is the closed
+// (cofactor) form in double rounded once. K = fx, fy, cx, cy of slamgpu_camera.
+inline void cv_mat3_mul(const float* a, const float* b, float* c) {
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      double acc = 0.0;
+      for (int k = 0; k < 3; ++k) acc += (double)a[3 * i + k] * (double)b[3 * k + j];
+      c[3 * i + j] = (float)acc;
+    }
+}
+inline void cv_mat3_inv(const float* a, float* o) {
+  const double a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4], a5 = a[5], a6 = a[6],
+               a7 = a[7], a8 = a[8];
+  const double det = a0 * (a4 * a8 - a5 * a7) - a1 * (a3 * a8 - a5 * a6) + a2 * (a3 * a7 - a4 * a6);
+  o[0] = (float)((a4 * a8 - a5 * a7) / det);
+  o[1] = (float)((a2 * a7 - a1 * a8) / det);
+  o[2] = (float)((a1 * a5 - a2 * a4) / det);
+  o[3] = (float)((a5 * a6 - a3 * a8) / det);
+  o[4] = (float)((a0 * a8 - a2 * a6) / det);
+  o[5] = (float)((a2 * a3 - a0 * a5) / det);
+  o[6] = (float)((a3 * a7 - a4 * a6) / det);
+  o[7] = (float)((a1 * a6 - a0 * a7) / det);
+  o[8] = (float)((a0 * a4 - a1 * a3) / det);
+}
+inline void compute_fundamental_matrix(const KeyFrameView& kf1, const KeyFrameView& kf2,
+                                       const slamgpu_camera& K1, const slamgpu_camera& K2,
+                                       float F12[9]) {
+  float R1[9], R2t[9], nR1[9], t1[3], t2[3];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) {
+      R1[3 * r + c] = kf1.Tcw[4 * r + c];
+      nR1[3 * r + c] = -kf1.Tcw[4 * r + c];
+      R2t[3 * c + r] = kf2.Tcw[4 * r + c];
+    }
+    t1[r] = kf1.Tcw[4 * r + 3];
+    t2[r] = kf2.Tcw[4 * r + 3];
+  }
+  float R12[9], m[9], t12[3];
+  cv_mat3_mul(R1, R2t, R12);
+  cv_mat3_mul(nR1, R2t, m);
+  for (int i = 0; i < 3; ++i) {
+    double acc = 0.0;
+    for (int k = 0; k < 3; ++k) acc += (double)m[3 * i + k] * (double)t2[k];
+    t12[i] = (float)acc + t1[i];
+  }
+  const float t12x[9] = {0.0f, -t12[2], t12[1], t12[2], 0.0f, -t12[0], -t12[1], t12[0], 0.0f};
+  const float K1t[9] = {K1.fx, 0.0f, 0.0f, 0.0f, K1.fy, 0.0f, K1.cx, K1.cy, 1.0f};
+  const float K2m[9] = {K2.fx, 0.0f, K2.cx, 0.0f, K2.fy, K2.cy, 0.0f, 0.0f, 1.0f};
+  float K1ti[9], K2i[9], a[9], b[9];
+  cv_mat3_inv(K1t, K1ti);
+  cv_mat3_inv(K2m, K2i);
+  cv_mat3_mul(K1ti, t12x, a);
+  cv_mat3_mul(a, R12, b);
+  cv_mat3_mul(b, K2i, F12);
+}
+
+// ---- LocalMapper::CreateNewMapPoints (local_mapper.cpp:258-492) ----------------------------------
+// What it reads of a KeyFrame beyond KeyFrameView and KeyFrameFeatures: depths, the raw keypoints
+// (UnprojectStereo, keyframe.cpp:478-492), fx fy cx cy mbf and mb.
+struct KeyFrameStereo {
+  const float* depths = nullptr;
+  const slamgpu_keypoint* kps = nullptr;  // KeyFrame::keypoints; nullptr = undistorted_keypoints
+  slamgpu_camera cam = {0, 0, 0, 0, 0};
+  float mb = 0;
+};
+
+// One `new MapPoint(x3D, current_keyframe_, map_)` with what :478-488 then does to it, for the
+// caller to replay: AddObservation(kfs[kf1], idx1), AddObservation(kfs[kf2], idx2), AddMapPoint on
+// both keyframes, descriptor (ComputeDistinctiveDescriptors), normal and min / max distance
+// (UpdateNormalAndDepth), Map::AddMapPoint, recently_added_map_points_.push_back.
+struct NewPoint {
+  float xyz[3];
+  int32_t kf1, idx1, kf2, idx2;
+  uint8_t desc[32];
+  float normal[3];
+  float min_dist, max_dist;
+  int32_t source;  // SLAMGPU_NP_DLT / _STEREO1 / _STEREO2
+};
+struct NewPointsResult {
+  std::vector<NewPoint> points;     // in the reference's order: neighbour, then vMatchedIndices
+  std::vector<uint8_t> skipped;     // [n_neighbours] the baseline test (:290-304) dropped it
+  std::vector<int8_t> status;       // [n_neighbours][n_kps of the current keyframe] SLAMGPU_NP_*
+  int n_kps = 0;
+};
+
+// neighbours: GetBestCovisibilityKeyFrames(is_monocular ? 20 : 10) as keyframe indices.
+// median_depth[k]: neighbour k's ComputeSceneMedianDepth(2), read only when is_monocular.
+// first_obs[k]: 0 when the current keyframe precedes neighbour k in a std::map<KeyFrame*, size_t>
+// (its address is the lower one), 1 otherwise: with two observations ComputeDistinctiveDescriptors
+// keeps the first entry's descriptor (map_point.cpp:287-298, both medians 0, strict <).
+// The baseline tests run here, everything else in one slamgpu_create_new_map_points call with
+// OrbMatcher(0.6f, false)'s check_ori = false. The reference's `if (i > 0 &&
+// CheckNewKeyFrames()) return;` (:285) maps to "use the rows of the first k neighbours": a
+// neighbour's points and status row do not depend on later neighbours, so a caller that sees a
+// new keyframe arrive applies points[.kf2 among the first k neighbours] and drops the rest, or
+// passes only the neighbours it wants. The search reads one calibration for all neighbours (the
+// first neighbour's; keyframes of one sensor share it).
+inline NewPointsResult create_new_map_points(int cur, const KeyFrameView* kfs,
+                                             const KeyFrameFeatures* features,
+                                             const KeyFrameStereo* stereo, const int32_t* neighbours,
+                                             int n_neighbours, bool is_monocular,
+                                             const float* median_depth, const int32_t* first_obs,
+                                             const slamgpu_levels& lv, bool check_ori = false) {
+  NewPointsResult out;
+  const KeyFrameView& K1 = kfs[cur];
+  out.n_kps = K1.n_kps;
+  out.skipped.assign(n_neighbours > 0 ? n_neighbours : 0, 0);
+  out.status.assign((size_t)(n_neighbours > 0 ? n_neighbours : 0) * K1.n_kps, 0);
+  if (n_neighbours <= 0) return out;
+  std::vector<KfRecord> rec;
+  rec.reserve(1 + n_neighbours);
+  std::vector<slamgpu_kf> hk(1 + n_neighbours);
+  std::vector<slamgpu_kf_stereo> hs(1 + n_neighbours);
+  std::vector<slamgpu_newpoints_nbor> nb(n_neighbours);
+  for (int k = -1; k < n_neighbours; ++k) {
+    const int idx = k < 0 ? cur : neighbours[k];
+    rec.push_back(kf_record(kfs[idx], features[idx]));
+    hk[k + 1] = rec.back().kf;
+    hs[k + 1].depth = stereo[idx].depths;
+    hs[k + 1].raw_kps = stereo[idx].kps;
+    hs[k + 1].cam = stereo[idx].cam;
+    hs[k + 1].mb = stereo[idx].mb;
+  }
+  const float* O1 = features[cur].Ow;
+  for (int k = 0; k < n_neighbours; ++k) {
+    const int idx = neighbours[k];
+    const float* O2 = features[idx].Ow;
+    double s = 0.0;  // cv::norm(nbor_pos - current_pos) (:292)
+    for (int c = 0; c < 3; ++c) {
+      const float d = O2[c] - O1[c];
+      s += (double)d * (double)d;
+    }
+    const float baseline = (float)std::sqrt(s);
+    bool skip;
+    if (is_monocular) skip = baseline / median_depth[k] < 0.01f;  // :294-299
+    else skip = baseline < stereo[idx].mb;                        // :300-304
+    out.skipped[k] = skip;
+    std::memset(&nb[k], 0, sizeof(nb[k]));
+    nb[k].kf2 = 1 + k;
+    nb[k].skip = skip ? 1 : 0;
+    nb[k].first_obs = first_obs[k];
+    if (!skip) compute_fundamental_matrix(K1, kfs[idx], stereo[cur].cam, stereo[idx].cam, nb[k].F12);
+  }
+  const int n1 = K1.n_kps;
+  std::vector<uint8_t> has_mp1(rec[0].has_mp);
+  std::vector<slamgpu_fuse_point> pts(n1 > 0 ? n1 : 1);
+  std::vector<slamgpu_new_point> news(n1 > 0 ? n1 : 1);
+  int n_new = 0;
+  throw_if(slamgpu_create_new_map_points(hk.data(), hs.data(), nb.data(), n_neighbours,
+                                         &stereo[neighbours[0]].cam, &lv, check_ori ? 1 : 0,
+                                         has_mp1.data(), pts.data(), news.data(),
+                                         out.status.empty() ? nullptr : out.status.data(), &n_new),
+           slamgpu_kfmatch_last_error);
+  if (n_new < 0)
+    throw std::runtime_error("slamgpu: create_new_map_points: a keyframe the search cannot take");
+  out.points.resize(n_new);
+  for (int i = 0; i < n_new; ++i) {
+    NewPoint& p = out.points[i];
+    for (int c = 0; c < 3; ++c) {
+      p.xyz[c] = pts[i].xyz[c];
+      p.normal[c] = pts[i].normal[c];
+    }
+    p.kf1 = cur;
+    p.idx1 = news[i].idx1;
+    p.kf2 = neighbours[news[i].neighbour];
+    p.idx2 = news[i].idx2;
+    std::memcpy(p.desc, pts[i].desc, 32);
+    p.min_dist = pts[i].min_dist;
+    p.max_dist = pts[i].max_dist;
+    p.source = news[i].source;
+  }
+  return out;
+}
+
 // ---- OrbMatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, float th)
 // (orb_matcher.cpp:804-954), LocalMapper::SearchInNeighbors (local_mapper.cpp:521, 540).
 // What Fuse reads of a map point beyond MapPointView: GetNormal(), min_dist_ / max_dist_ and

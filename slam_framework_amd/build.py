@@ -45,6 +45,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_initializer_adapter_check()
         build_reloc_adapter_check()
         build_initmatch_adapter_check()
+        build_newpoints_adapter_check()
         build_device_math_check()
         return LIB
     objdir = os.path.join(PKG, "build")
@@ -79,6 +80,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_initializer_adapter_check()
     build_reloc_adapter_check()
     build_initmatch_adapter_check()
+    build_newpoints_adapter_check()
     build_device_math_check()
     return LIB
 
@@ -215,6 +217,26 @@ def build_initmatch_adapter_check() -> str:
                     "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", INITMATCH_ADAPTER_BIN],
                    check=True)
     return INITMATCH_ADAPTER_BIN
+
+
+NEWPOINTS_ADAPTER_SRC = os.path.join(ROOT, "tests", "newpoints_adapter_check.cpp")
+NEWPOINTS_ADAPTER_BIN = os.path.join(ROOT, "tests", "newpoints_adapter_check")
+
+
+def build_newpoints_adapter_check() -> str:
+    """g++ build of tests/newpoints_adapter_check.cpp: compute_fundamental_matrix and
+    create_new_map_points of include/slamgpu_adapters.hpp (LocalMapper::CreateNewMapPoints,
+    local_mapper.cpp:258-492: the baseline tests, the one device call, the NewPoint actions)
+    driven from C++ against libslamgpu.so."""
+    deps = [NEWPOINTS_ADAPTER_SRC, LIB] + glob.glob(os.path.join(ROOT, "include", "*.h*"))
+    if os.path.exists(NEWPOINTS_ADAPTER_BIN) and os.path.getmtime(NEWPOINTS_ADAPTER_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return NEWPOINTS_ADAPTER_BIN
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I",
+                    os.path.join(ROOT, "include"), NEWPOINTS_ADAPTER_SRC, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", NEWPOINTS_ADAPTER_BIN],
+                   check=True)
+    return NEWPOINTS_ADAPTER_BIN
 
 
 GEOMETRY_SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")

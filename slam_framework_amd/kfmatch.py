@@ -10,6 +10,9 @@ and of include/slamgpu_loopmatch.h, the LoopCloser's three Sim3 matchers:
   search_by_projection_sim3  OrbMatcher::SearchByProjection(pKF, Scw, ...) (:384-497)
   fuse_sim3                  OrbMatcher::Fuse(pKF, Scw, ...) (:956-1079), the candidate search;
                              fuse_sim3_apply is the reference's per-point tail (:1061-1075)
+  create_new_map_points      LocalMapper::CreateNewMapPoints (local_mapper.cpp:258-492): the chain
+                             over the neighbours, search and triangulation, in one device call;
+                             compute_fundamental_matrix is its ComputeFundamentalMatrix (:615-630)
 libslamgpu.so is the only compute path (no CPU fallback); errors raise SlamGpuError.
 """
 from __future__ import annotations
@@ -41,6 +44,23 @@ SIM3_PAIR_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("mp1_begin", "<i4")
 assert FUSE_POINT_DTYPE.itemsize == 80 and TRI_PAIR_DTYPE.itemsize == 48
 assert SBP_JOB_DTYPE.itemsize == 16 and SIM3_PAIR_DTYPE.itemsize == 112
 assert KF_DTYPE.itemsize == 128
+# CreateNewMapPoints: slamgpu_kf_stereo (device addresses), slamgpu_newpoints_nbor / _job,
+# slamgpu_new_point
+KF_STEREO_DTYPE = np.dtype([("depth", "<u8"), ("raw_kps", "<u8"), ("cam", "<f4", (5,)),
+                            ("mb", "<f4")])
+NP_NBOR_DTYPE = np.dtype([("kf2", "<i4"), ("F12", "<f4", (9,)), ("skip", "<i4"),
+                          ("first_obs", "<i4")])
+NP_JOB_DTYPE = np.dtype([("kf1", "<i4"), ("first_nbor", "<i4"), ("n_nbors", "<i4"),
+                         ("pad", "<i4"), ("has_mp1", "<u8")])
+NEW_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"),
+                            ("source", "<i4")])
+assert KF_STEREO_DTYPE.itemsize == 40 and NP_NBOR_DTYPE.itemsize == 48
+assert NP_JOB_DTYPE.itemsize == 24 and NEW_POINT_DTYPE.itemsize == 16
+# per-keypoint status of one neighbour (SLAMGPU_NP_*)
+NP_DLT, NP_STEREO1, NP_STEREO2 = 1, 2, 3
+NP_W_ZERO, NP_LOW_PARALLAX, NP_BEHIND1, NP_BEHIND2 = -1, -2, -3, -4
+NP_REPROJ1_STEREO, NP_REPROJ1_MONO, NP_REPROJ2_STEREO, NP_REPROJ2_MONO = -5, -6, -7, -8
+NP_DIST_ZERO, NP_SCALE, NP_NO_DEPTH, NP_MALFORMED = -9, -10, -11, -12
 
 
 class Levels(C.Structure):
@@ -60,6 +80,17 @@ class Kf(C.Structure):
                                           "node_start", "node_feats")] + [
         ("n", C.c_int32), ("n_nodes", C.c_int32), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3),
         ("Ow", C.c_float * 3), ("pad", C.c_float)]
+
+
+class KfStereo(C.Structure):
+    """slamgpu_kf_stereo (host pointers in the synchronous call)."""
+    _fields_ = [("depth", C.c_void_p), ("raw_kps", C.c_void_p), ("cam", G.Camera),
+                ("mb", C.c_float)]
+
+
+class NewPointsNbor(C.Structure):
+    _fields_ = [("kf2", C.c_int32), ("F12", C.c_float * 9), ("skip", C.c_int32),
+                ("first_obs", C.c_int32)]
 
 
 def levels(scale_factor=1.2, nlevels=8):
@@ -106,6 +137,14 @@ def lib():
                                    C.POINTER(Levels), C.POINTER(KfGrid), vp, vp, C.POINTER(ip)]
         L.slamgpu_fuse_device.argtypes = [vp, vp, vp, ip, C.c_float, C.POINTER(G.Camera),
                                           C.POINTER(Levels), C.POINTER(KfGrid), vp, vp, vp]
+        L.slamgpu_create_new_map_points_scratch_bytes.argtypes = [ip, ip]
+        L.slamgpu_create_new_map_points_scratch_bytes.restype = C.c_size_t
+        L.slamgpu_create_new_map_points_device.argtypes = [
+            vp, vp, vp, ip, vp, ip, C.POINTER(G.Camera), C.POINTER(Levels), ip, vp, vp, vp,
+            C.c_int64, vp, C.c_int64, vp, C.c_size_t, vp]
+        L.slamgpu_create_new_map_points.argtypes = [
+            C.POINTER(Kf), C.POINTER(KfStereo), C.POINTER(NewPointsNbor), ip, C.POINTER(G.Camera),
+            C.POINTER(Levels), ip, vp, vp, vp, vp, C.POINTER(ip)]
         cp, lp, gp, fl = C.POINTER(G.Camera), C.POINTER(Levels), C.POINTER(KfGrid), C.c_float
         L.slamgpu_loopmatch_last_error.argtypes = []
         L.slamgpu_loopmatch_last_error.restype = C.c_char_p
@@ -220,6 +259,114 @@ def fuse_device(d_kfs, d_pts, d_point_kf, n_pts, th, cam, lv, grid, d_best_idx, 
     _check(lib().slamgpu_fuse_device(_dev(d_kfs), _dev(d_pts), _dev(d_point_kf), n_pts, float(th),
                                      C.byref(_cam(cam)), C.byref(lv), C.byref(grid),
                                      _dev(d_best_idx), _dev(d_best_dist), C.c_void_p(stream or 0)))
+
+
+# ---- CreateNewMapPoints ------------------------------------------------------------------------
+def _mat3(a, b):
+    """cv::Mat product of two 3 x 3 float matrices: double sums over ascending k, rounded once."""
+    out = np.zeros((3, 3), np.float32)
+    for i in range(3):
+        for j in range(3):
+            acc = 0.0
+            for k in range(3):
+                acc += float(a[i, k]) * float(b[k, j])
+            out[i, j] = np.float32(acc)
+    return out
+
+
+def compute_fundamental_matrix(Tcw1, Tcw2, cam1, cam2):
+    """LocalMapper::ComputeFundamentalMatrix (local_mapper.cpp:615-630) under the cv::Mat rules of
+    DESIGN.md "CreateNewMapPoints": R12 = R1w * R2w.t(); t12 = -R1w * R2w.t() * t2w + t1w;
+    F12 = K1.t().inv() * t12x * R12 * K2.inv(), every product left to right as written, the two
+    inverses in the closed (cofactor) form in double, rounded once. Bit for bit what
+    compute_fundamental_matrix of include/slamgpu_adapters.hpp gives.
+    cam = (fx, fy, cx, cy, ...). Returns 3 x 3 f32."""
+    T1, T2 = np.asarray(Tcw1, np.float32), np.asarray(Tcw2, np.float32)
+    R1, t1, R2, t2 = T1[:3, :3], T1[:3, 3], T2[:3, :3], T2[:3, 3]
+    R2t = np.ascontiguousarray(R2.T)
+    R12 = _mat3(R1, R2t)
+    nR1 = (-R1).astype(np.float32)
+    m = _mat3(nR1, R2t)
+    t12 = np.zeros(3, np.float32)
+    for i in range(3):
+        acc = 0.0
+        for k in range(3):
+            acc += float(m[i, k]) * float(t2[k])
+        t12[i] = np.float32(np.float32(acc) + t1[i])
+    tx = np.array([[0, -t12[2], t12[1]], [t12[2], 0, -t12[0]], [-t12[1], t12[0], 0]], np.float32)
+
+    def kmat(c):
+        fx, fy, cx, cy = [np.float32(v) for v in c[:4]]
+        return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float32)
+
+    def inv3(m):
+        a = [float(v) for v in m.reshape(-1)]
+        det = (a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) +
+               a[2] * (a[3] * a[7] - a[4] * a[6]))
+        cof = [a[4] * a[8] - a[5] * a[7], a[2] * a[7] - a[1] * a[8], a[1] * a[5] - a[2] * a[4],
+               a[5] * a[6] - a[3] * a[8], a[0] * a[8] - a[2] * a[6], a[2] * a[3] - a[0] * a[5],
+               a[3] * a[7] - a[4] * a[6], a[1] * a[6] - a[0] * a[7], a[0] * a[4] - a[1] * a[3]]
+        return np.array([np.float32(c / det) for c in cof], np.float32).reshape(3, 3)
+    K1ti = inv3(np.ascontiguousarray(kmat(cam1).T))
+    return _mat3(_mat3(_mat3(K1ti, tx), R12), inv3(kmat(cam2)))
+
+
+def host_kf_stereo(depth, cam, mb, raw_kps=None):
+    """A slamgpu_kf_stereo over host arrays (kept alive in the returned tuple). cam = (fx, fy, cx,
+    cy, mbf) of this keyframe."""
+    d = np.ascontiguousarray(depth, np.float32)
+    raw = None
+    if raw_kps is not None:
+        raw = np.ascontiguousarray(raw_kps)
+        raw = raw if raw.dtype == G.KP_DTYPE else raw.view(G.KP_DTYPE)
+    s = KfStereo()
+    s.depth, s.raw_kps, s.cam, s.mb = _p(d), _p(raw), _cam(cam), float(np.float32(mb))
+    return s, [d, raw]
+
+
+def create_new_map_points(cur, cur_stereo, nbors, cam, lv, check_ori=True):
+    """cur / cur_stereo: (Kf, keep) from host_kf (with has_mp and feature_vec) and host_kf_stereo.
+    nbors: [(kf, kf_stereo, F12, skip, first_obs)] in GetBestCovisibilityKeyFrames order; skip =
+    the baseline test of local_mapper.cpp:290-304 failed. cam: the neighbours' fx, fy, cx, cy.
+    Returns (n_new, points FUSE_POINT_DTYPE, news NEW_POINT_DTYPE, status [len(nbors)][n1] i8,
+    has_mp1 u8 [n1] after the call); n_new = -1 when a search reported -1."""
+    n1, nn = cur[0].n, len(nbors)
+    kfs = (Kf * (1 + nn))(cur[0], *[b[0][0] for b in nbors])
+    sts = (KfStereo * (1 + nn))(cur_stereo[0], *[b[1][0] for b in nbors])
+    hn = (NewPointsNbor * max(nn, 1))()
+    for k, b in enumerate(nbors):
+        hn[k].kf2 = 1 + k
+        hn[k].F12[:] = [float(x) for x in np.asarray(b[2], np.float32).reshape(9)]
+        hn[k].skip, hn[k].first_obs = int(bool(b[3])), int(b[4])
+    has_mp1 = np.zeros(max(n1, 1), np.uint8)
+    if n1:
+        has_mp1[:n1] = np.ctypeslib.as_array(C.cast(cur[0].has_mp, C.POINTER(C.c_uint8)), (n1,))
+    points = np.zeros(max(n1, 1), FUSE_POINT_DTYPE)
+    news = np.zeros(max(n1, 1), NEW_POINT_DTYPE)
+    status = np.zeros((max(nn, 1), max(n1, 1)), np.int8)
+    out = C.c_int()
+    _check(lib().slamgpu_create_new_map_points(kfs, sts, hn, nn, C.byref(_cam(cam)), C.byref(lv),
+                                               int(bool(check_ori)), _p(has_mp1), _p(points),
+                                               _p(news), _p(status), C.byref(out)))
+    n = max(out.value, 0)
+    st = status.reshape(-1)[:nn * n1].reshape(nn, n1)
+    return out.value, points[:n], news[:n], st, has_mp1[:n1]
+
+
+def create_new_map_points_scratch_bytes(n_jobs, max_nbors):
+    return int(lib().slamgpu_create_new_map_points_scratch_bytes(int(n_jobs), int(max_nbors)))
+
+
+def create_new_map_points_device(d_kfs, d_kf_stereo, d_jobs, n_jobs, d_nbors, max_nbors, cam, lv,
+                                 check_ori, d_n_new, d_points, d_new, point_stride, d_status,
+                                 status_stride, d_scratch, scratch_bytes, stream=None):
+    """Every job's chain on `stream`, no synchronisation (include/slamgpu_kfmatch.h)."""
+    from .bow import _dev
+    _check(lib().slamgpu_create_new_map_points_device(
+        _dev(d_kfs), _dev(d_kf_stereo), _dev(d_jobs), n_jobs, _dev(d_nbors), max_nbors,
+        C.byref(_cam(cam)), C.byref(lv), int(bool(check_ori)), _dev(d_n_new), _dev(d_points),
+        _dev(d_new), point_stride, _dev(d_status), status_stride, _dev(d_scratch), scratch_bytes,
+        C.c_void_p(stream or 0)))
 
 
 def fuse_apply(best_idx, kf_map_points, mp_ids, mp_nobs, mp_bad, mp_in_kf):

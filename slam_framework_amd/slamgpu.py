@@ -131,6 +131,8 @@ EXPORTS = [
     # include/slamgpu_kfmatch.h
     "slamgpu_kfmatch_last_error", "slamgpu_search_for_triangulation",
     "slamgpu_search_for_triangulation_device", "slamgpu_fuse", "slamgpu_fuse_device",
+    "slamgpu_create_new_map_points", "slamgpu_create_new_map_points_device",
+    "slamgpu_create_new_map_points_scratch_bytes",
     # include/slamgpu_loopmatch.h
     "slamgpu_loopmatch_last_error", "slamgpu_fuse_sim3", "slamgpu_fuse_sim3_device",
     "slamgpu_search_by_projection_sim3", "slamgpu_search_by_projection_sim3_scratch_bytes",
