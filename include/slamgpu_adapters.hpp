@@ -27,6 +27,7 @@
 #include "slamgpu.h"
 #include "slamgpu_bow.h"
 #include "slamgpu_initializer.h"
+#include "slamgpu_kfdb.h"
 #include "slamgpu_kfmatch.h"
 #include "slamgpu_loopmatch.h"
 #include "slamgpu_optimizer.h"
@@ -2092,5 +2093,120 @@ inline int search_for_initialization(slamgpu_ctx* ctx, int frame, const FrameVie
   if (rc != SLAMGPU_OK) throw std::runtime_error(std::string("slamgpu: ") + slamgpu_last_error(ctx));
   return nm;
 }
+
+// ---- KeyframeDatabase queries (include/slamgpu_kfdb.h), LoopCloser::DetectLoop
+// (src/core/loop_closer.cpp:194-297) -------------------------------------------------------------
+// The id lists of slamgpu_kfdb_detect_loop_candidates for keyframe `cur` of the keyframe array:
+// connected = GetConnectedKeyFrames() (the caller's set, as keyframe indices, in any order),
+// covisible = GetVectorCovisibleKeyFrames() with the bad ones dropped (loop_closer.cpp:215-218),
+// both as KeyFrame::Id()s, which are the database's slots.
+struct LoopQueryIds {
+  int32_t kf_id;
+  std::vector<int32_t> connected, covisible;
+};
+inline LoopQueryIds gather_detect_loop_candidates(int cur, const KeyFrameView* kfs,
+                                                  const int32_t* connected, int n_connected) {
+  LoopQueryIds q;
+  q.kf_id = (int32_t)kfs[cur].id;
+  for (int i = 0; i < n_connected; i++) q.connected.push_back((int32_t)kfs[connected[i]].id);
+  for (int i = 0; i < kfs[cur].n_covisible; i++) {
+    const KeyFrameView& k = kfs[kfs[cur].covisible[i]];
+    if (!k.bad) q.covisible.push_back((int32_t)k.id);
+  }
+  return q;
+}
+
+// One synchronous query with the gathered lists; returns the candidate ids in the reference's
+// order and *min_score. Throws on an error.
+inline std::vector<int32_t> detect_loop_candidates(slamgpu_kfdb* db, const LoopQueryIds& q,
+                                                   int max_keyframes, float* min_score) {
+  std::vector<int32_t> cand((size_t)max_keyframes);
+  int n = 0;
+  throw_if(slamgpu_kfdb_detect_loop_candidates(db, q.kf_id, q.connected.data(),
+                                               (int)q.connected.size(), q.covisible.data(),
+                                               (int)q.covisible.size(), min_score, cand.data(), &n,
+                                               nullptr, nullptr),
+           slamgpu_kfdb_last_error);
+  cand.resize((size_t)n);
+  return cand;
+}
+
+// The rest of DetectLoop on the host: the consistency groups of loop_closer.cpp:239-296 kept as
+// sorted sets of keyframe ids, the way Sim3SolverCore replays iterate / find. The caller's
+// DetectLoop becomes
+//   if (core.too_soon(id)) { db add(id); return false; }                              // :204-208
+//   cand = detect_loop_candidates(...);
+//   r = core.update(cand.data(), cand.size(), connected_of);  db add(id);   // :227-232, :289
+//   return r.detected;   // consistent_enough_candidates_ = r.consistent_enough
+// Every exit adds the current keyframe to the database: Result::add_current_keyframe is true on
+// all of them and early_exit() says so for the first.
+class LoopDetectorCore {
+ public:
+  using Group = std::pair<std::vector<int32_t>, int>;  // ConsistentGroup: (sorted ids, counter)
+  struct Result {
+    std::vector<int32_t> consistent_enough;  // consistent_enough_candidates_, in candidate order
+    bool add_current_keyframe;               // keyframe_db_->add(current_keyframe_)
+    bool detected;                           // DetectLoop's return value
+  };
+
+  explicit LoopDetectorCore(int covisibility_consistency_threshold = 3)
+      : threshold_(covisibility_consistency_threshold) {}
+
+  int64_t last_loop_kf_id = 0;  // last_loop_kf_id_: the caller sets it where CorrectLoop does
+
+  // loop_closer.cpp:204: fewer than 10 keyframes since the last loop -- no query at all.
+  bool too_soon(int64_t kf_id) const { return kf_id < last_loop_kf_id + 10; }
+  static Result early_exit() { return Result{{}, true, false}; }
+
+  // connected_of(id, out): appends GetConnectedKeyFrames() of candidate `id` to out (any order).
+  template <class ConnectedOf>
+  Result update(const int32_t* candidates, int n, ConnectedOf connected_of) {
+    Result r{{}, true, false};
+    if (n == 0) {  // :227-232
+      groups_.clear();
+      return r;
+    }
+    std::vector<Group> current;
+    std::vector<bool> visited(groups_.size(), false);
+    for (int c = 0; c < n; c++) {
+      std::vector<int32_t> group;
+      connected_of(candidates[c], group);
+      group.push_back(candidates[c]);
+      std::sort(group.begin(), group.end());
+      group.erase(std::unique(group.begin(), group.end()), group.end());
+      bool has_enough = false, consistent_for_some = false;
+      for (size_t g = 0; g < groups_.size(); g++) {
+        const std::vector<int32_t>& prev = groups_[g].first;
+        bool consistent = false;
+        for (int32_t id : group)
+          if (std::binary_search(prev.begin(), prev.end(), id)) {
+            consistent = true;
+            consistent_for_some = true;
+            break;
+          }
+        if (!consistent) continue;
+        const int n_current = groups_[g].second + 1;
+        if (!visited[g]) {  // :267-270: a previous group is extended once per query
+          current.emplace_back(group, n_current);
+          visited[g] = true;
+        }
+        if (n_current >= threshold_ && !has_enough) {
+          r.consistent_enough.push_back(candidates[c]);
+          has_enough = true;
+        }
+      }
+      if (!consistent_for_some) current.emplace_back(group, 0);  // :280-282
+    }
+    groups_ = std::move(current);  // :286
+    r.detected = !r.consistent_enough.empty();
+    return r;
+  }
+
+  const std::vector<Group>& groups() const { return groups_; }
+
+ private:
+  int threshold_;
+  std::vector<Group> groups_;
+};
 
 }  // namespace slamgpu_adapter

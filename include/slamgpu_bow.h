@@ -99,6 +99,35 @@ int slamgpu_bow_transform_device(slamgpu_vocab* v, const uint8_t* d_desc, int64_
                                  const int32_t* d_counts, int count_step, int n_sets,
                                  int levelsup, const slamgpu_bow_sets* out, void* stream);
 
+/* ---- score -------------------------------------------------------------------------------- */
+/* One BowVector: words[n] ascending with their values (host pointers). */
+typedef struct {
+  const uint32_t* words;
+  const double* values;
+  int32_t n;
+  int32_t pad;
+} slamgpu_bow_vec;
+/* Device twin; the count is a device pointer so that a view can point at one set of
+ * slamgpu_bow_transform_device outputs. */
+typedef struct {
+  const uint32_t* words;
+  const double* values;
+  const int32_t* n;
+} slamgpu_bow_vec_view;
+
+/* Replaces TemplatedVocabulary::score(v1, v2) (TemplatedVocabulary.h) -> L1Scoring::score
+ * (ScoringObject.cpp:23-68) for n_pairs independent pairs (a[p], b[p]): the sum of
+ * fabs(vi - wi) - fabs(vi) - fabs(wi) over the common words, one addition after another in
+ * ascending word order in FP64, then -score / 2.0: scores[p] is the reference's double bit for
+ * bit. Only SLAMGPU_L1_NORM (what ORBvoc uses) is built: for a vocabulary with one of the other
+ * five scorings both calls return SLAMGPU_EINVAL with a message that names the scoring. */
+int slamgpu_bow_score(const slamgpu_vocab* v, const slamgpu_bow_vec* a, const slamgpu_bow_vec* b,
+                      int n_pairs, double* scores);
+/* d_a, d_b: arrays of n_pairs views in device memory. */
+int slamgpu_bow_score_device(const slamgpu_vocab* v, const slamgpu_bow_vec_view* d_a,
+                             const slamgpu_bow_vec_view* d_b, int n_pairs, double* d_scores,
+                             void* stream);
+
 /* ---- SearchByBoW -------------------------------------------------------------------------- */
 /* One side of a SearchByBoW call (host pointers). A = the keyframe whose features are iterated
  * (pKF / pKF1), B = the other view (F / pKF2). valid[i]: feature i's map point exists and is not

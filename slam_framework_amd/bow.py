@@ -69,6 +69,31 @@ def lib():
         L.slamgpu_search_by_bow_device.argtypes = [vp, vp, ip, ip, C.c_float, ip, vp, i64, vp, vp]
         L.slamgpu_distinctive_descriptors.argtypes = [vp, vp, ip, vp, vp]
         L.slamgpu_distinctive_descriptors_device.argtypes = [vp, vp, ip, vp, vp, vp]
+        L.slamgpu_bow_score.argtypes = [vp, vp, vp, ip, vp]
+        L.slamgpu_bow_score_device.argtypes = [vp, vp, vp, ip, vp, vp]
+        L.slamgpu_kfdb_last_error.argtypes = []
+        L.slamgpu_kfdb_last_error.restype = C.c_char_p
+        L.slamgpu_kfdb_create.argtypes = [ip, ip, ip, C.POINTER(vp)]
+        L.slamgpu_kfdb_destroy.argtypes = [vp]
+        L.slamgpu_kfdb_destroy.restype = None
+        L.slamgpu_kfdb_set_bow.argtypes = [vp, ip, vp, vp, ip]
+        L.slamgpu_kfdb_set_bow_device.argtypes = [vp, ip, vp, vp, vp, vp]
+        L.slamgpu_kfdb_set_covisible.argtypes = [vp, ip, vp, ip]
+        L.slamgpu_kfdb_set_covisible_device.argtypes = [vp, ip, vp, ip, vp]
+        for name in ("add", "erase"):
+            getattr(L, f"slamgpu_kfdb_{name}").argtypes = [vp, ip]
+            getattr(L, f"slamgpu_kfdb_{name}_device").argtypes = [vp, ip, vp]
+        L.slamgpu_kfdb_clear.argtypes = [vp]
+        L.slamgpu_kfdb_clear_device.argtypes = [vp, vp]
+        L.slamgpu_kfdb_detect_scratch_bytes.argtypes = [vp]
+        L.slamgpu_kfdb_detect_scratch_bytes.restype = sz
+        L.slamgpu_kfdb_detect_loop_candidates.argtypes = [vp, ip, vp, ip, vp, ip, vp, vp,
+                                                          C.POINTER(ip), vp, vp]
+        L.slamgpu_kfdb_detect_loop_candidates_device.argtypes = [vp, ip, vp, ip, vp, ip, vp, vp,
+                                                                 vp, vp, vp, vp, vp]
+        L.slamgpu_kfdb_detect_relocalization_candidates.argtypes = [vp, vp, vp, ip, vp,
+                                                                    C.POINTER(ip), vp, vp]
+        L.slamgpu_kfdb_detect_relocalization_candidates_device.argtypes = [vp] * 10
         L.slamgpu_gray.argtypes = [vp, sz, ip, ip, ip, ip, vp, sz]
         L.slamgpu_gray_device.argtypes = [vp, sz, sz, ip, ip, ip, ip, ip, vp, sz, sz, vp]
         _bound = True
@@ -199,6 +224,30 @@ class ORBVocabulary:
                                                   _dev(d_counts), count_step, n_sets, levelsup,
                                                   C.byref(sets.struct), C.c_void_p(stream or 0)))
 
+    def score(self, v1, v2):
+        """TemplatedVocabulary::score(v1, v2) (L1 only): the reference's double."""
+        return self.score_pairs([v1], [v2])[0]
+
+    def score_pairs(self, a, b):
+        """score for len(a) independent pairs of BowVectors -> f64 array."""
+        n = len(a)
+        keep, arr = [], (BowVec * (2 * max(n, 1)))()
+        for k, v in enumerate(list(a) + list(b)):
+            w = np.ascontiguousarray(v.words, np.uint32)
+            x = np.ascontiguousarray(v.values, np.float64)
+            keep.append((w, x))
+            arr[k] = BowVec(_p(w), _p(x), len(w), 0)
+        out = np.zeros(max(n, 1), np.float64)
+        _check(lib().slamgpu_bow_score(self.h, C.byref(arr), C.byref(arr, n * C.sizeof(BowVec)),
+                                       n, _p(out)))
+        del keep
+        return out[:n]
+
+    def score_device(self, d_a_views, d_b_views, n_pairs, d_scores, stream=None):
+        """d_*_views: device arrays of slamgpu_bow_vec_view (3 x u64: words, values, n)."""
+        _check(lib().slamgpu_bow_score_device(self.h, _dev(d_a_views), _dev(d_b_views), n_pairs,
+                                              _dev(d_scores), C.c_void_p(stream or 0)))
+
     def close(self):
         if getattr(self, "h", None):
             lib().slamgpu_vocab_destroy(self.h)
@@ -209,6 +258,140 @@ class ORBVocabulary:
             self.close()
         except Exception:
             pass
+
+
+class BowVec(C.Structure):
+    """slamgpu_bow_vec: one BowVector (host pointers)."""
+    _fields_ = [("words", C.c_void_p), ("values", C.c_void_p), ("n", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+def _check_kfdb(rc):
+    if rc != 0:
+        raise G.SlamGpuError(f"slamgpu error {rc}: {lib().slamgpu_kfdb_last_error().decode()}")
+
+
+class KeyFrameDatabase:
+    """KeyframeDatabase (src/data/keyframe_database.cpp) resident on one device: binding of
+    include/slamgpu_kfdb.h. A keyframe's slot is its id. The plain methods take numpy arrays and
+    synchronise; the *_device methods take torch tensors (or device addresses) and a stream and
+    return without synchronising."""
+
+    MAX_NEIGHBOURS = 10
+
+    def __init__(self, max_keyframes, max_words=MAX_FEATURES, device=0):
+        self.max_keyframes, self.max_words, self.device = max_keyframes, max_words, device
+        self.h = None
+        h = C.c_void_p()
+        _check_kfdb(lib().slamgpu_kfdb_create(device, max_keyframes, max_words, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slamgpu_kfdb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ---- host forms ----
+    def set_bow(self, kf_id, words, values=None):
+        """KeyFrame::ComputeBoW's BowVector: (words, values) or a BowVector."""
+        if values is None:
+            words, values = words.words, words.values
+        w = np.ascontiguousarray(words, np.uint32)
+        v = np.ascontiguousarray(values, np.float64)
+        _check_kfdb(lib().slamgpu_kfdb_set_bow(self.h, kf_id, _p(w), _p(v), len(w)))
+
+    def set_covisible(self, kf_id, ids):
+        """GetBestCovisibilityKeyFrames(10) of the keyframe, in order."""
+        a = np.ascontiguousarray(ids, np.int32)
+        _check_kfdb(lib().slamgpu_kfdb_set_covisible(self.h, kf_id, _p(a), len(a)))
+
+    def add(self, kf_id):
+        _check_kfdb(lib().slamgpu_kfdb_add(self.h, kf_id))
+
+    def erase(self, kf_id):
+        _check_kfdb(lib().slamgpu_kfdb_erase(self.h, kf_id))
+
+    def clear(self):
+        _check_kfdb(lib().slamgpu_kfdb_clear(self.h))
+
+    def _diag(self, diagnostics):
+        if not diagnostics:
+            return None, None
+        return np.zeros(self.max_keyframes, np.int32), np.zeros(self.max_keyframes, np.float32)
+
+    def DetectLoopCandidates(self, kf_id, connected, covisible, diagnostics=False):
+        """DetectLoopCandidates(pKF, minScore) with DetectLoop's minScore over `covisible`.
+        -> (candidate ids, min_score f32[, common words, scores])."""
+        con = np.ascontiguousarray(connected, np.int32)
+        cov = np.ascontiguousarray(covisible, np.int32)
+        ms, cand = np.zeros(1, np.float32), np.zeros(self.max_keyframes, np.int32)
+        n = C.c_int()
+        cw, sc = self._diag(diagnostics)
+        _check_kfdb(lib().slamgpu_kfdb_detect_loop_candidates(
+            self.h, kf_id, _p(con), len(con), _p(cov), len(cov), _p(ms), _p(cand), C.byref(n),
+            _p(cw), _p(sc)))
+        out = (cand[:n.value].copy(), ms[0])
+        return out + (cw, sc) if diagnostics else out
+
+    def DetectRelocalizationCandidates(self, words, values=None, diagnostics=False):
+        """DetectRelocalizationCandidates(frame) for the frame's BowVector.
+        -> candidate ids[, common words, scores]."""
+        if values is None:
+            words, values = words.words, words.values
+        w = np.ascontiguousarray(words, np.uint32)
+        v = np.ascontiguousarray(values, np.float64)
+        cand = np.zeros(self.max_keyframes, np.int32)
+        n = C.c_int()
+        cw, sc = self._diag(diagnostics)
+        _check_kfdb(lib().slamgpu_kfdb_detect_relocalization_candidates(
+            self.h, _p(w), _p(v), len(w), _p(cand), C.byref(n), _p(cw), _p(sc)))
+        out = cand[:n.value].copy()
+        return (out, cw, sc) if diagnostics else out
+
+    # ---- device forms ----
+    def scratch_bytes(self):
+        return int(lib().slamgpu_kfdb_detect_scratch_bytes(self.h))
+
+    def set_bow_device(self, kf_id, d_words, d_values, d_n, stream=None):
+        """d_n: device int32 count, e.g. one entry of DeviceBowSets.n_words."""
+        _check_kfdb(lib().slamgpu_kfdb_set_bow_device(self.h, kf_id, _dev(d_words),
+                                                      _dev(d_values), _dev(d_n),
+                                                      C.c_void_p(stream or 0)))
+
+    def set_covisible_device(self, kf_id, d_ids, n, stream=None):
+        _check_kfdb(lib().slamgpu_kfdb_set_covisible_device(self.h, kf_id, _dev(d_ids), n,
+                                                            C.c_void_p(stream or 0)))
+
+    def add_device(self, kf_id, stream=None):
+        _check_kfdb(lib().slamgpu_kfdb_add_device(self.h, kf_id, C.c_void_p(stream or 0)))
+
+    def erase_device(self, kf_id, stream=None):
+        _check_kfdb(lib().slamgpu_kfdb_erase_device(self.h, kf_id, C.c_void_p(stream or 0)))
+
+    def clear_device(self, stream=None):
+        _check_kfdb(lib().slamgpu_kfdb_clear_device(self.h, C.c_void_p(stream or 0)))
+
+    def DetectLoopCandidates_device(self, kf_id, d_connected, n_connected, d_covisible,
+                                    n_covisible, d_min_score, d_candidates, d_n_candidates,
+                                    d_scratch, d_common_words=None, d_scores=None, stream=None):
+        _check_kfdb(lib().slamgpu_kfdb_detect_loop_candidates_device(
+            self.h, kf_id, _dev(d_connected), n_connected, _dev(d_covisible), n_covisible,
+            _dev(d_min_score), _dev(d_candidates), _dev(d_n_candidates), _dev(d_common_words),
+            _dev(d_scores), _dev(d_scratch), C.c_void_p(stream or 0)))
+
+    def DetectRelocalizationCandidates_device(self, d_words, d_values, d_n, d_candidates,
+                                              d_n_candidates, d_scratch, d_common_words=None,
+                                              d_scores=None, stream=None):
+        _check_kfdb(lib().slamgpu_kfdb_detect_relocalization_candidates_device(
+            self.h, _dev(d_words), _dev(d_values), _dev(d_n), _dev(d_candidates),
+            _dev(d_n_candidates), _dev(d_common_words), _dev(d_scores), _dev(d_scratch),
+            C.c_void_p(stream or 0)))
 
 
 class DeviceBowSets:

@@ -46,6 +46,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_reloc_adapter_check()
         build_initmatch_adapter_check()
         build_newpoints_adapter_check()
+        build_kfdb_adapter_check()
         build_device_math_check()
         return LIB
     objdir = os.path.join(PKG, "build")
@@ -81,6 +82,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_reloc_adapter_check()
     build_initmatch_adapter_check()
     build_newpoints_adapter_check()
+    build_kfdb_adapter_check()
     build_device_math_check()
     return LIB
 
@@ -237,6 +239,25 @@ def build_newpoints_adapter_check() -> str:
                     "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", NEWPOINTS_ADAPTER_BIN],
                    check=True)
     return NEWPOINTS_ADAPTER_BIN
+
+
+KFDB_ADAPTER_SRC = os.path.join(ROOT, "tests", "kfdb_adapter_check.cpp")
+KFDB_ADAPTER_BIN = os.path.join(ROOT, "tests", "kfdb_adapter_check")
+
+
+def build_kfdb_adapter_check() -> str:
+    """g++ build of tests/kfdb_adapter_check.cpp: gather_detect_loop_candidates and
+    LoopDetectorCore of include/slamgpu_adapters.hpp (LoopCloser::DetectLoop's consistency groups,
+    loop_closer.cpp:194-297, around the database query) driven from C++ on the CPU."""
+    deps = [KFDB_ADAPTER_SRC, LIB] + glob.glob(os.path.join(ROOT, "include", "*.h*"))
+    if os.path.exists(KFDB_ADAPTER_BIN) and os.path.getmtime(KFDB_ADAPTER_BIN) >= max(
+            os.path.getmtime(d) for d in deps):
+        return KFDB_ADAPTER_BIN
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-I",
+                    os.path.join(ROOT, "include"), KFDB_ADAPTER_SRC, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", KFDB_ADAPTER_BIN],
+                   check=True)
+    return KFDB_ADAPTER_BIN
 
 
 GEOMETRY_SRC = os.path.join(ROOT, "tests", "geometry_check.cpp")

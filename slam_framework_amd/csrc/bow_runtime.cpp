@@ -13,10 +13,12 @@
 #include "../../include/slamgpu_bow.h"
 #include "bow_kernels.h"
 #include "host_stage.h"
+#include "kfdb_kernels.h"
 #include "stage_layout.h"
 
 using namespace slamgpu;
 
+static_assert(sizeof(slamgpu_bow_vec_view) == sizeof(BowVecView), "slamgpu_bow_vec_view layout");
 static_assert(sizeof(slamgpu_bow_view) == sizeof(BowView), "slamgpu_bow_view layout");
 static_assert(sizeof(slamgpu_keypoint) == sizeof(KeyPoint), "keypoint layout");
 
@@ -305,6 +307,76 @@ int slamgpu_bow_transform(slamgpu_vocab* v, const uint8_t* desc, int n, int leve
   HIPCHECK(t_bow_err, hipStreamSynchronize(st));
   *n_words = nw;
   *n_nodes = nn;
+  return 0;
+}
+
+// Only L1Scoring is built; the message names what the vocabulary asks for.
+static int check_scoring(const slamgpu_vocab* v) {
+  static const char* const names[6] = {"L1_NORM", "L2_NORM", "CHI_SQUARE", "KL", "BHATTACHARYYA",
+                                       "DOT_PRODUCT"};
+  if (!v) return t_bow_err.fail(SLAMGPU_EINVAL, "NULL vocabulary");
+  if (v->scoring != SLAMGPU_L1_NORM)
+    return t_bow_err.fail(SLAMGPU_EINVAL, "score: the vocabulary's scoring %s is not built (only L1_NORM)",
+                          names[v->scoring]);
+  return 0;
+}
+
+int slamgpu_bow_score_device(const slamgpu_vocab* v, const slamgpu_bow_vec_view* d_a,
+                             const slamgpu_bow_vec_view* d_b, int n_pairs, double* d_scores,
+                             void* stream) {
+  if (int r = check_scoring(v)) return r;
+  if (n_pairs < 0) return t_bow_err.fail(SLAMGPU_EINVAL, "n_pairs %d < 0", n_pairs);
+  if (n_pairs == 0) return 0;
+  if (!d_a || !d_b || !d_scores) return t_bow_err.fail(SLAMGPU_EINVAL, "NULL device buffer");
+  HIPCHECK(t_bow_err, hipSetDevice(v->device));
+  HIPCHECK(t_bow_err, launch_bow_score(reinterpret_cast<const BowVecView*>(d_a),
+                                       reinterpret_cast<const BowVecView*>(d_b), n_pairs, d_scores,
+                                       static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+int slamgpu_bow_score(const slamgpu_vocab* v, const slamgpu_bow_vec* a, const slamgpu_bow_vec* b,
+                      int n_pairs, double* scores) {
+  if (int r = check_scoring(v)) return r;
+  if (n_pairs < 0) return t_bow_err.fail(SLAMGPU_EINVAL, "n_pairs %d < 0", n_pairs);
+  if (n_pairs == 0) return 0;
+  if (!a || !b || !scores) return t_bow_err.fail(SLAMGPU_EINVAL, "NULL argument");
+  size_t total = 0;
+  for (int p = 0; p < n_pairs; p++)
+    for (const slamgpu_bow_vec* s : {&a[p], &b[p]}) {
+      if (s->n < 0 || (s->n > 0 && (!s->words || !s->values)))
+        return t_bow_err.fail(SLAMGPU_EINVAL, "pair %d: bad BowVector (n %d)", p, s->n);
+      for (int i = 1; i < s->n; i++)
+        if (s->words[i] <= s->words[i - 1])
+          return t_bow_err.fail(SLAMGPU_EINVAL, "pair %d: words not strictly ascending", p);
+      total += (size_t)s->n;
+    }
+  HIPCHECK(t_bow_err, hipSetDevice(v->device));
+  StageLease S(t_bow_err);
+  StageLayout L;
+  const BowScoreLayout l = layout_bow_score(L, n_pairs, total);
+  if (int r = S.reserve(L.size())) return r;
+  // views[p] = a[p], views[n_pairs + p] = b[p]
+  std::vector<slamgpu_bow_vec_view> views(2 * (size_t)n_pairs);
+  std::vector<int32_t> counts(2 * (size_t)n_pairs);
+  size_t at = 0;
+  for (int side = 0; side < 2; side++)
+    for (int p = 0; p < n_pairs; p++) {
+      const slamgpu_bow_vec& s = side ? b[p] : a[p];
+      const size_t k = (size_t)side * n_pairs + p;
+      HIPCHECK(t_bow_err, S.upload(l.words + at * 4, s.words, (size_t)s.n * 4));
+      HIPCHECK(t_bow_err, S.upload(l.values + at * 8, s.values, (size_t)s.n * 8));
+      counts[k] = s.n;
+      views[k] = {S.at<uint32_t>(l.words) + at, S.at<double>(l.values) + at,
+                  S.at<int32_t>(l.counts) + k};
+      at += (size_t)s.n;
+    }
+  HIPCHECK(t_bow_err, S.upload(l.counts, counts.data(), counts.size() * 4));
+  HIPCHECK(t_bow_err, S.upload(l.views, views.data(), views.size() * sizeof(views[0])));
+  const BowVecView* dv = S.at<BowVecView>(l.views);
+  HIPCHECK(t_bow_err, launch_bow_score(dv, dv + n_pairs, n_pairs, S.at<double>(l.scores), S.stream()));
+  HIPCHECK(t_bow_err, S.download(scores, l.scores, (size_t)n_pairs * 8));
+  HIPCHECK(t_bow_err, hipStreamSynchronize(S.stream()));
   return 0;
 }
 

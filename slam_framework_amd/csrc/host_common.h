@@ -35,7 +35,8 @@ struct ErrorSlot {
 
 extern thread_local ErrorSlot t_opt_err;     // slamgpu_optimizer_last_error
 extern thread_local ErrorSlot t_bow_err;     // slamgpu_bow_last_error
-extern thread_local ErrorSlot t_kf_err;      // slamgpu_kfmatch_last_error == slamgpu_loopmatch_last_error
+extern thread_local ErrorSlot t_kfdb_err;    // slamgpu_kfdb_last_error
+extern thread_local ErrorSlot t_kf_err;     // slamgpu_kfmatch_last_error == slamgpu_loopmatch_last_error
 extern thread_local ErrorSlot t_s3_err;      // slamgpu_sim3solver_last_error
 extern thread_local ErrorSlot t_pnp_err;     // slamgpu_pnpsolver_last_error
 extern thread_local ErrorSlot t_init_err;    // slamgpu_initializer_last_error

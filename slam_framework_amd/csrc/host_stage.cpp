@@ -6,6 +6,7 @@ namespace slamgpu {
 
 thread_local ErrorSlot t_opt_err;
 thread_local ErrorSlot t_bow_err;
+thread_local ErrorSlot t_kfdb_err;
 thread_local ErrorSlot t_kf_err;
 thread_local ErrorSlot t_s3_err;
 thread_local ErrorSlot t_pnp_err;

@@ -206,6 +206,32 @@ inline InitSearchLayout layout_init_search(StageLayout& L, size_t n1) {
 }
 
 // A host FeatureVector (n_nodes > 0) must be well formed before its indices reach the device:
+// slamgpu_bow_score of n_pairs pairs: both sides' words and values packed back to back
+// (total_words entries each), their counts and the views that point at them.
+struct BowScoreLayout { size_t words, values, counts, views, scores; };
+inline BowScoreLayout layout_bow_score(StageLayout& L, size_t n_pairs, size_t total_words) {
+  return {L.take<uint32_t>(total_words), L.take<double>(total_words),
+          L.take<int32_t>(2 * n_pairs), L.take<slamgpu_bow_vec_view>(2 * n_pairs),
+          L.take<double>(n_pairs)};
+}
+
+// One BowVector on its way into the database, or a relocalisation query's.
+struct KfdbVecLayout { size_t words, values, n; };
+inline KfdbVecLayout layout_kfdb_vec(StageLayout& L, size_t n) {
+  return {L.take<uint32_t>(n), L.take<double>(n), L.take<int32_t>(1)};
+}
+// A detect call: the id lists of the loop query, the outputs ([0, out_end) from min_score on come
+// back), the scratch.
+struct KfdbDetectLayout {
+  size_t connected, covisible, min_score, n_candidates, candidates, common_words, scores, scratch;
+};
+inline KfdbDetectLayout layout_kfdb_detect(StageLayout& L, size_t max_kf, size_t n_connected,
+                                           size_t n_covisible, size_t scratch_bytes) {
+  return {L.take<int32_t>(n_connected), L.take<int32_t>(n_covisible), L.take<float>(1),
+          L.take<int32_t>(1), L.take<int32_t>(max_kf), L.take<int32_t>(max_kf),
+          L.take<float>(max_kf), L.take(scratch_bytes)};
+}
+
 // node_start[0] == 0 and ascending within [0, n], nodes strictly ascending, feature indices < n.
 // feat_fmt is the caller's wording of the last failure; it is given (name, index).
 inline int check_feature_vector(ErrorSlot& err, const char* name, int n, int n_nodes,

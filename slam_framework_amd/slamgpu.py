@@ -127,7 +127,16 @@ EXPORTS = [
     "slamgpu_vocab_destroy", "slamgpu_vocab_info", "slamgpu_vocab_nodes", "slamgpu_bow_transform",
     "slamgpu_bow_transform_device", "slamgpu_search_by_bow", "slamgpu_search_by_bow_device",
     "slamgpu_distinctive_descriptors", "slamgpu_distinctive_descriptors_device", "slamgpu_gray",
-    "slamgpu_gray_device",
+    "slamgpu_gray_device", "slamgpu_bow_score", "slamgpu_bow_score_device",
+    # include/slamgpu_kfdb.h
+    "slamgpu_kfdb_last_error", "slamgpu_kfdb_create", "slamgpu_kfdb_destroy",
+    "slamgpu_kfdb_set_bow", "slamgpu_kfdb_set_bow_device", "slamgpu_kfdb_set_covisible",
+    "slamgpu_kfdb_set_covisible_device", "slamgpu_kfdb_add", "slamgpu_kfdb_erase",
+    "slamgpu_kfdb_clear", "slamgpu_kfdb_add_device", "slamgpu_kfdb_erase_device",
+    "slamgpu_kfdb_clear_device", "slamgpu_kfdb_detect_scratch_bytes",
+    "slamgpu_kfdb_detect_loop_candidates", "slamgpu_kfdb_detect_loop_candidates_device",
+    "slamgpu_kfdb_detect_relocalization_candidates",
+    "slamgpu_kfdb_detect_relocalization_candidates_device",
     # include/slamgpu_kfmatch.h
     "slamgpu_kfmatch_last_error", "slamgpu_search_for_triangulation",
     "slamgpu_search_for_triangulation_device", "slamgpu_fuse", "slamgpu_fuse_device",
