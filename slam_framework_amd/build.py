@@ -48,6 +48,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         build_newpoints_adapter_check()
         build_kfdb_adapter_check()
         build_device_math_check()
+        build_eg_step_check()
         return LIB
     objdir = os.path.join(PKG, "build")
     os.makedirs(objdir, exist_ok=True)
@@ -84,6 +85,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     build_newpoints_adapter_check()
     build_kfdb_adapter_check()
     build_device_math_check()
+    build_eg_step_check()
     return LIB
 
 
@@ -304,6 +306,19 @@ def build_host_stage_check() -> str:
     return HOST_STAGE_BIN
 
 
+def _build_device_harness(exe: str, srcs, deps) -> str:
+    """hipcc build, with the library's own FLAGS, of a stand-alone program under tests/ that
+    includes library .hip files and links libslamgpu.so; skipped while `exe` is no older than any
+    of `deps`."""
+    if os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(d) for d in deps):
+        return exe
+    tmp = exe + ".tmp"
+    subprocess.run([HIPCC, *FLAGS, *srcs, "-L", PKG, "-lslamgpu",
+                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", tmp], check=True)
+    os.replace(tmp, exe)
+    return exe
+
+
 DEVICE_MATH_SRCS = [os.path.join(ROOT, "tests", n) for n in (
     "device_math_check.hip", "device_math_check_sim3.hip", "device_math_check_eg.hip")]
 DEVICE_MATH_BIN = os.path.join(ROOT, "tests", "device_math_check")
@@ -317,14 +332,25 @@ def build_device_math_check() -> str:
     deps = DEVICE_MATH_SRCS + [os.path.join(ROOT, "tests", "device_math_check.h"), LIB]
     deps += glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hip"))
     deps += glob.glob(os.path.join(ROOT, "include", "*.h"))
-    if os.path.exists(DEVICE_MATH_BIN) and os.path.getmtime(DEVICE_MATH_BIN) >= max(
-            os.path.getmtime(d) for d in deps):
-        return DEVICE_MATH_BIN
-    tmp = DEVICE_MATH_BIN + ".tmp"
-    subprocess.run([HIPCC, *FLAGS, *DEVICE_MATH_SRCS, "-L", PKG, "-lslamgpu",
-                    "-Wl,-rpath,$ORIGIN/../slam_framework_amd", "-o", tmp], check=True)
-    os.replace(tmp, DEVICE_MATH_BIN)
-    return DEVICE_MATH_BIN
+    return _build_device_harness(DEVICE_MATH_BIN, DEVICE_MATH_SRCS, deps)
+
+
+EG_STEP_SRC = os.path.join(ROOT, "tests", "eg_step_check.hip")
+EG_STEP_BIN = os.path.join(ROOT, "tests", "eg_step_check")
+
+
+def build_eg_step_check():
+    """hipcc build of tests/eg_step_check.hip with the library's own FLAGS: a stand-alone program
+    that includes eg_kernels.hip and csrc/eg_structure.h and runs one linear step of
+    OptimizeEssentialGraph (products, assembly, both factor-solve variants) and the small kernels
+    around it on given graphs. Linked to libslamgpu.so only for the symbols the included
+    launchers refer to. The program belongs to the tests: in a tree that does not hold its source
+    there is nothing to build and None is returned (the tests that run it assert that it exists)."""
+    if not os.path.exists(EG_STEP_SRC):
+        return None
+    deps = [EG_STEP_SRC, LIB] + glob.glob(os.path.join(CSRC, "*.h"))
+    deps += [os.path.join(CSRC, "eg_kernels.hip")] + glob.glob(os.path.join(ROOT, "include", "*.h"))
+    return _build_device_harness(EG_STEP_BIN, [EG_STEP_SRC], deps)
 
 
 if __name__ == "__main__":

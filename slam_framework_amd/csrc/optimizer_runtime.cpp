@@ -24,6 +24,7 @@
 #include "ba_coop.h"
 #include "ba_kernels.h"
 #include "eg_kernels.h"
+#include "eg_structure.h"
 #include "host_stage.h"
 #include "pose_kernels.h"
 #include "sim3_kernels.h"
@@ -646,67 +647,10 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
                     point_ref[q], n_kf);
   if (n_kf == 0) return 0;
   // ---- the graph's structure (host): free vertices, profile, assembly targets, extents ----
-  std::vector<int32_t> fidx(n_kf);
-  int F = 0;
-  for (int v = 0; v < n_kf; v++) fidx[v] = fixed[v] ? -1 : F++;
-  std::vector<int32_t> start(F);
-  for (int f = 0; f < F; f++) start[f] = f;
-  for (int k = 0; k < n_edges; k++) {
-    const int a = fidx[edges[k].i], b = fidx[edges[k].j];
-    if (a < 0 || b < 0) continue;
-    const int hi = std::max(a, b), lo = std::min(a, b);
-    start[hi] = std::min(start[hi], lo);
-  }
-  std::vector<int64_t> off(F + 1, 0);
-  for (int f = 0; f < F; f++) off[f + 1] = off[f] + (f - start[f] + 1);
-  const int64_t n_blocks = off[F];
-  std::vector<std::vector<int32_t>> items(F);
-  std::vector<int32_t> tgt_block, tgt_vertex;
-  std::vector<std::vector<int32_t>> off_items;
-  std::vector<std::pair<int64_t, int32_t>> off_key;  // (block, target) of off-diagonal targets
-  std::vector<int32_t> block_target;
-  {
-    std::vector<int32_t> blk2t((size_t)n_blocks, -1);
-    for (int k = 0; k < n_edges; k++) {
-      const int a = fidx[edges[k].i], b = fidx[edges[k].j];
-      if (a >= 0) items[a].push_back(4 * k + 0);
-      if (b >= 0) items[b].push_back(4 * k + 1);
-      if (a >= 0 && b >= 0) {
-        const int hi = std::max(a, b), lo = std::min(a, b);
-        const int64_t blk = off[hi] + (lo - start[hi]);
-        if (blk2t[blk] < 0) {
-          blk2t[blk] = (int32_t)off_items.size();
-          off_items.emplace_back();
-          off_key.emplace_back(blk, 0);
-        }
-        off_items[blk2t[blk]].push_back(4 * k + (a > b ? 2 : 3));
-      }
-    }
-  }
-  std::vector<int32_t> tgt_ptr(1, 0), tgt_items;
-  for (int f = 0; f < F; f++) {
-    tgt_block.push_back((int32_t)(off[f] + (f - start[f])));
-    tgt_vertex.push_back(f);
-    tgt_items.insert(tgt_items.end(), items[f].begin(), items[f].end());
-    tgt_ptr.push_back((int32_t)tgt_items.size());
-  }
-  for (size_t t = 0; t < off_items.size(); t++) {
-    tgt_block.push_back((int32_t)off_key[t].first);
-    tgt_vertex.push_back(-1);
-    tgt_items.insert(tgt_items.end(), off_items[t].begin(), off_items[t].end());
-    tgt_ptr.push_back((int32_t)tgt_items.size());
-  }
-  const int n_targets = (int)tgt_block.size();
-  std::vector<std::vector<int32_t>> ext(F);
-  for (int i = 0; i < F; i++)
-    for (int k = start[i]; k < i; k++) ext[k].push_back(i);
-  std::vector<int32_t> ext_ptr(1, 0), ext_rows;
-  std::vector<int64_t> ext_base;
-  for (int k = 0; k < F; k++) {
-    ext_rows.insert(ext_rows.end(), ext[k].begin(), ext[k].end());
-    for (int i : ext[k]) ext_base.push_back(off[i] - start[i]);
-    ext_ptr.push_back((int32_t)ext_rows.size());
-  }
+  const EgStructure gs = eg_build_structure(n_kf, fixed, edges, n_edges);
+  const int F = gs.F;
+  const int64_t n_blocks = gs.n_blocks;
+  const int n_targets = (int)gs.tgt_block.size();
   // ---- one device region: inputs, structure, state ----
   const size_t E = (size_t)n_edges, N = (size_t)n_kf, P7 = 7 * (size_t)F;
   StageLease HS(t_opt_err);
@@ -714,9 +658,9 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
   const size_t o_edges = L.take(E * sizeof(slamgpu_sim3_edge)), o_fidx = L.take(4 * N);
   const size_t o_start = L.take(4 * (size_t)F), o_off = L.take(8 * ((size_t)F + 1));
   const size_t o_tb = L.take(4 * (size_t)n_targets), o_tv = L.take(4 * (size_t)n_targets);
-  const size_t o_tp = L.take(4 * ((size_t)n_targets + 1)), o_ti = L.take(4 * tgt_items.size());
-  const size_t o_ep = L.take(4 * ((size_t)F + 1)), o_er = L.take(4 * ext_rows.size());
-  const size_t o_eb = L.take(8 * ext_base.size());
+  const size_t o_tp = L.take(4 * ((size_t)n_targets + 1)), o_ti = L.take(4 * gs.tgt_items.size());
+  const size_t o_ep = L.take(4 * ((size_t)F + 1)), o_er = L.take(4 * gs.ext_rows.size());
+  const size_t o_eb = L.take(8 * gs.ext_base.size());
   const size_t o_S = L.take(8 * 8 * N), o_S2 = L.take(8 * 8 * N), o_S0 = L.take(8 * 8 * N);
   const size_t o_err = L.take(8 * 7 * E), o_chi = L.take(8 * E), o_con = L.take(8 * kEgContrib * E);
   const size_t o_J = L.take(8 * 98 * E);
@@ -729,16 +673,16 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
   char* d = HS.at<char>(0);
   hipStream_t st = HS.stream();
   HIPCHECK(t_opt_err, HS.upload(o_edges, edges, E * sizeof(slamgpu_sim3_edge)));
-  HIPCHECK(t_opt_err, HS.upload(o_fidx, fidx.data(), 4 * N));
-  HIPCHECK(t_opt_err, HS.upload(o_start, start.data(), 4 * (size_t)F));
-  HIPCHECK(t_opt_err, HS.upload(o_off, off.data(), 8 * ((size_t)F + 1)));
-  HIPCHECK(t_opt_err, HS.upload(o_tb, tgt_block.data(), 4 * (size_t)n_targets));
-  HIPCHECK(t_opt_err, HS.upload(o_tv, tgt_vertex.data(), 4 * (size_t)n_targets));
-  HIPCHECK(t_opt_err, HS.upload(o_tp, tgt_ptr.data(), 4 * ((size_t)n_targets + 1)));
-  HIPCHECK(t_opt_err, HS.upload(o_ti, tgt_items.data(), 4 * tgt_items.size()));
-  HIPCHECK(t_opt_err, HS.upload(o_ep, ext_ptr.data(), 4 * ((size_t)F + 1)));
-  HIPCHECK(t_opt_err, HS.upload(o_er, ext_rows.data(), 4 * ext_rows.size()));
-  HIPCHECK(t_opt_err, HS.upload(o_eb, ext_base.data(), 8 * ext_base.size()));
+  HIPCHECK(t_opt_err, HS.upload(o_fidx, gs.fidx.data(), 4 * N));
+  HIPCHECK(t_opt_err, HS.upload(o_start, gs.start.data(), 4 * (size_t)F));
+  HIPCHECK(t_opt_err, HS.upload(o_off, gs.off.data(), 8 * ((size_t)F + 1)));
+  HIPCHECK(t_opt_err, HS.upload(o_tb, gs.tgt_block.data(), 4 * (size_t)n_targets));
+  HIPCHECK(t_opt_err, HS.upload(o_tv, gs.tgt_vertex.data(), 4 * (size_t)n_targets));
+  HIPCHECK(t_opt_err, HS.upload(o_tp, gs.tgt_ptr.data(), 4 * ((size_t)n_targets + 1)));
+  HIPCHECK(t_opt_err, HS.upload(o_ti, gs.tgt_items.data(), 4 * gs.tgt_items.size()));
+  HIPCHECK(t_opt_err, HS.upload(o_ep, gs.ext_ptr.data(), 4 * ((size_t)F + 1)));
+  HIPCHECK(t_opt_err, HS.upload(o_er, gs.ext_rows.data(), 4 * gs.ext_rows.size()));
+  HIPCHECK(t_opt_err, HS.upload(o_eb, gs.ext_base.data(), 8 * gs.ext_base.size()));
   HIPCHECK(t_opt_err, HS.upload(o_S, Scw, 64 * N));
   HIPCHECK(t_opt_err, HS.upload(o_S0, Scw, 64 * N));
   HIPCHECK(t_opt_err, hipMemsetAsync(d + o_x, 0, 8 * P7 + 1, st));
@@ -763,7 +707,7 @@ int slamgpu_optimize_essential_graph(int n_kf, double* Scw, const uint8_t* fixed
   G.ext_ptr = reinterpret_cast<const int32_t*>(d + o_ep);
   G.ext_rows = reinterpret_cast<const int32_t*>(d + o_er);
   G.ext_base = reinterpret_cast<const int64_t*>(d + o_eb);
-  G.n_ext = (int)ext_rows.size();
+  G.n_ext = (int)gs.ext_rows.size();
   G.n_blocks = n_blocks;
   EgState W;
   W.S = reinterpret_cast<double*>(d + o_S);

@@ -10,7 +10,19 @@ where either LM run stops); recovered poses and corrected points follow. A free-
 noisy measurements is ill-conditioned along the scale walk (lambda stays ~1e-16): there the
 LM stops after a few iterations (ten failed trials at lambda ~1e-16 against the numeric
 Jacobians' noise), at a point that rounding moves: chi2 within 1e-3 relative, Sim3s within
-1e-4 x |S - S_init| (tools/eg_diag.py shows both runs stopping at the same iteration)."""
+1e-4 x |S - S_init| (tools/eg_diag.py shows both runs stopping at the same iteration).
+
+The largest case under the tight tolerance, (12, 130, True, None, (100, 30)): 129 free vertices,
+loop rows that reach 70 and 128 columns back. It is chosen by what the oracle alone says. The LM
+stop rule (three iterations that lower chi2 by less than 1e-3 of it) can end a run while the
+estimates still move along the soft modes of a ring anchored at one vertex, whose condition grows
+with n^2; a case is well-conditioned for this comparison when the oracle's result is a fixed point
+of the oracle (a second run started from it moves nothing), as it is on the 80-keyframe case.
+Seed 12 is the smallest seed from 7 on of which that holds at 130 keyframes
+(tests/test_eg_oracle.py checks it). On a case without that property, such as
+(7, 200, True, None, (150, 40)), the comparison is of two stopping points, not of two solvers;
+tests/test_eg_step_gpu.py holds the linear step itself to 1e-14 at these sizes and beyond.
+"""
 import numpy as np
 import pytest
 
@@ -33,6 +45,8 @@ CASES = [  # (seed, n_kf, fix_scale, meas_noise, old_loop)
     (4, 40, True, 0.0, None),
     (5, 120, False, 0.002, (90, 30)),
     (6, 8, True, None, None),
+    # 129 free vertices under the tight tolerance; the oracle's result is its own fixed point (above)
+    (12, 130, True, None, (100, 30)),
 ]
 
 

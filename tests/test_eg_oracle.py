@@ -90,6 +90,24 @@ def test_reference_graph_runs_and_lowers_chi2():
     assert _chi2(S1, E) < chi0 and its > 0
 
 
+def test_large_tight_case_is_a_fixed_point_of_the_oracle():
+    """What makes (12, 130, True, None, (100, 30)) the large case of tests/test_eg_gpu.py's tight
+    tolerance: a second oracle run started from the first one's result moves nothing, so where
+    the LM stop rule ends the run is not in question. Seed 12 is the smallest of seeds 7 .. 26 of
+    which that holds at 130 keyframes with the reference's own measurements; the issue-sized
+    (7, 200, True, None, (150, 40)) is not such a case."""
+    def moved(seed, n, old):
+        Scw, fixed, E, _, _ = S.essential_graph_problem(seed, n, fix_scale=True, old_loop=old)
+        S1, _, its = O.optimize_essential_graph(Scw, fixed, E, fix_scale=True)
+        S2, _, _ = O.optimize_essential_graph(S1, fixed, E, fix_scale=True)
+        assert its > 0
+        return np.abs(S2 - S1).max()
+
+    assert moved(12, 130, (100, 30)) == 0.0
+    assert all(moved(seed, 130, (100, 30)) > 0.0 for seed in range(7, 12))
+    assert moved(7, 200, (150, 40)) > 1e-5
+
+
 def test_correct_points():
     rng = np.random.default_rng(2)
     Sb = np.stack([O.sim3_exp(np.concatenate([rng.normal(0, 0.3, 3), rng.normal(0, 2, 3),
